@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """AOI tick benchmark (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--full adds every other leg to that line (the CPU baselines, the per-stage
+breakdown ticks, the claims, small-flush, host-I/O, sync and wire legs, the
+C++ host tick, and the config-4 and config-5 sub-records), each in runs of its
+own around the same timed region.  --dump-outputs DIR writes what the last
+timed step returned (its enter / leave events, and every timed step's event
+counts) as float64 .npy files, for comparing two builds on the same inputs.
 
 A step is one AOI flush (gwaoi_tick_device): one batch of Moved calls --
 every entity of the space moves once, in a seeded random call order -- then
@@ -15,9 +23,14 @@ RCCL) every rank owns its own independent space of the same size (GoWorld
 spaces are independent, Space.go:33): weak scaling, no data-path collective.
 
 Printed: one JSON line with value = entity-moves/s over all ranks, plus
-events/s, p50/p99 tick latency, the roofline of the dominant kernel (HIP
-events on the world's stream) and the CPU baseline (the go-aoi restatement in
-oracle/, one core, on a bounded sample of the same workload).
+events/s, p50/p99 tick latency and the roofline of the dominant kernel (HIP
+events on the world's stream); with --full also the CPU baseline (the go-aoi
+restatement in oracle/, one core, on a bounded sample of the same workload)
+and the other legs.
+
+At most MAX_BATCHES distinct move batches are generated; a longer run walks
+them forwards and backwards (every batch holds absolute positions, so each
+step still moves every entity once by one U(-1,1) step).
 """
 from __future__ import annotations
 
@@ -44,6 +57,79 @@ WORKLOAD_DESC = {
     "cfg5": "single 2^24-entity world uniform (L=sqrt(N*1250)), step U(-1,1), tiled into one x-strip per rank "
             "with halo exchange over RCCL",
 }
+
+
+MAX_BATCHES = 64  # distinct move batches generated per run (12 MB of HBM each at 1M entities)
+DUMP_BYTES = 64 << 20  # --dump-outputs: upper bound of everything written
+
+
+def batch_index(t: int, n_batches: int) -> int:
+    """The batch tick t applies: 0 .. n_batches-1 forwards, then backwards to 0, and so on.
+    A batch holds absolute positions, so a neighbouring batch in either direction is one
+    U(-1,1) step of every entity away."""
+    if n_batches < 2:
+        return 0
+    p = t % (2 * n_batches - 2)
+    return p if p < n_batches else 2 * n_batches - 2 - p
+
+
+def generate_batches(wl, ticks, threads: int = 8) -> list:
+    """[wl.tick(t) for t in ticks], bit for bit, advancing wl the same way: the random
+    parts of every tick (steps and call order depend on the seed and t alone) drawn
+    on `threads` threads, the walk itself applied in order."""
+    from concurrent.futures import ThreadPoolExecutor
+    from goworld_amd.workload import permutation, splitmix, subseed, unit_f64
+    ticks = list(ticks)
+    if wl.name == "cfg1" or len(ticks) < 2:
+        return [wl.tick(t) for t in ticks]
+    n = wl.n
+
+    def draw(t):  # Workload.tick's draws for tick t
+        r = splitmix(subseed(wl.seed, 0x71C, t), 2 * n)
+        sx = (2.0 * unit_f64(r[0:n]) - 1.0).astype(np.float32)
+        sz = (2.0 * unit_f64(r[n:2 * n]) - 1.0).astype(np.float32)
+        return sx, sz, permutation(subseed(wl.seed, 0x0D3, t), n)
+
+    out = []
+    with ThreadPoolExecutor(max(1, min(threads, cpu_cores()))) as pool:
+        for sx, sz, order in pool.map(draw, ticks):
+            wl.x = (wl.x + sx).astype(np.float32)
+            wl.z = (wl.z + sz).astype(np.float32)
+            out.append((order, wl.x[order], wl.z[order]))
+    return out
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """Write each array as path/<name>.npy in float64, DUMP_BYTES at most in all: an array
+    over its share is cut to a fixed seeded sample of its rows (in order).  Returns
+    {name: [rows written, rows]}."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    rows = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        keep = share // (8 * max(1, int(np.prod(a.shape[1:]))))
+        total = a.shape[0]
+        if total > keep:
+            a = a[np.sort(np.random.default_rng(0x5EEDD0).choice(total, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float64))
+        rows[name] = [int(a.shape[0]), int(total)]
+    return rows
+
+
+def device_pairs(ptr, k: int) -> np.ndarray:
+    """k (a, b) uint32 event pairs at device address ptr, copied to the host and sorted by
+    (a, b): the order inside a flush's event array is not part of the contract."""
+    import ctypes as C
+    a = np.empty((k, 2), np.uint32)
+    if k:
+        hip = C.CDLL("libamdhip64.so")
+        hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        rc = hip.hipMemcpy(a.ctypes.data, ptr, a.nbytes, 2)  # hipMemcpyDeviceToHost
+        if rc:
+            raise RuntimeError(f"hipMemcpy of {k} event pairs: error {rc}")
+        a = a[np.lexsort((a[:, 1], a[:, 0]))]
+    return a
 
 
 def dist_env():
@@ -1103,7 +1189,7 @@ def cfg5_job(args, ws, rank, local):
     port = int(os.environ.get("MASTER_PORT", "0") or 0)
     env.update(RANK=str(rank), LOCAL_RANK=str(local), WORLD_SIZE=str(ws), LOCAL_WORLD_SIZE=str(ws),
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port + 1 if port else _free_port()))
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cfg5", "--gpus", str(ws), "--steps",
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", "cfg5", "--gpus", str(ws), "--steps",
            str(args.cfg5_steps), "--warmup", str(args.cfg5_warmup), "--dist-backend", args.dist_backend,
            "--json-out", out, "--cpu-seconds", str(args.cfg5_cpu_seconds), "--strip-counts", args.strip_counts]
     if args.cfg5_entities:
@@ -1228,7 +1314,20 @@ def main():
     ap.add_argument("--cfg4-cpu-seconds", type=float, default=10.0,
                     help="CPU-XZ of the cfg4 sub-record on all cores (rank 0 at N=1; 0 = off)")
     ap.add_argument("--json-out", default=None, help="write the JSON line to this file instead of stdout")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: the CPU baselines, the stage breakdown ticks, the claims, "
+                         "small-flush, host-I/O, sync and wire legs, the C++ host tick, the config-4 and config-5 "
+                         "sub-records (their own options size them; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they returned as DIR/<name>.npy (float64): the last "
+                         "step's enter and leave events, sorted (a, b) pairs, and every timed step's event counts")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "cfg5":
+        ap.error("--dump-outputs: not available for the strip run (--workload cfg5)")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the headline
+        args.no_cpu_baseline = True
+        args.breakdown_steps = args.sync_steps = args.host_io_steps = args.host_tick_steps = 0
+        args.cfg4_steps = args.cfg5_steps = args.wire_steps = args.claims_steps = args.small_flush_reps = 0
 
     # --gpus N without an outside launcher: spawn the N ranks here, before anything touches the GPU
     try:
@@ -1296,6 +1395,7 @@ def main():
     t_setup = time.perf_counter()
     wl = wl_factory()
     n = wl.n
+    initial = wl.initial()  # the positions before the first batch (wl advances through the batches)
     bd = 0 if args.no_timing else max(0, args.breakdown_steps)
     timed_end = args.warmup + args.steps
     ticks = timed_end + bd
@@ -1303,10 +1403,11 @@ def main():
     # ---- synthetic move batches, generated before timing, resident in HBM
     import torch
     torch.cuda.set_device(device)
-    batches = []
-    for t in range(ticks):
-        sl, nx, nz = wl.tick(t)
-        batches.append((sl, nx, nz))
+    n_batches = min(ticks, MAX_BATCHES)  # a longer run walks them forwards and backwards (batch_index)
+    batches = generate_batches(wl, range(n_batches))
+    which = [batch_index(t, n_batches) for t in range(ticks)]  # tick -> its batch
+    last_batch = batches[which[-1]]  # every entity's position after the last tick (the legs below go on from there)
+    wl.x[last_batch[0]], wl.z[last_batch[0]] = last_batch[1], last_batch[2]
     # PCIe-inclusive leg (host memory): three untimed warmup ticks (one serial, two pipelined: they
     # allocate both pinned staging buffers) + hio serial + hio + 1 pipelined
     host_batches = [wl.tick(ticks + t) for t in range(4 * hio + 17 if hio else 0)]
@@ -1315,8 +1416,7 @@ def main():
     d_slots = torch.from_numpy(np.stack([b[0] for b in batches]).astype(np.int32)).to(f"cuda:{device}")
     d_x = torch.from_numpy(np.stack([b[1] for b in batches])).to(f"cuda:{device}")
     d_z = torch.from_numpy(np.stack([b[2] for b in batches])).to(f"cuda:{device}")
-    moves_per_tick = [b[0].size for b in batches]
-    last_batch = batches[-1]  # every entity's position after the last tick (the small-flush leg moves from there)
+    moves_per_tick = [batches[k][0].size for k in which]
     del batches
     torch.cuda.synchronize()
 
@@ -1326,10 +1426,7 @@ def main():
     w = World(n, max_spaces=wl.n_spaces, device=device, cells_per_dist=args.cells_per_dist,
               unique_moves=not args.claims)
     spaces = [w.space_create(wl.D) for _ in range(wl.n_spaces)]
-    wl0 = wl_factory()  # initial positions (wl has advanced through the batches)
-    initial = wl0.initial()
     slots, x0, z0, sp = initial
-    del wl0
     for s in range(wl.n_spaces):
         sel = np.nonzero(sp == s)[0] if wl.n_spaces > 1 else slice(None)
         w.enter_batch(spaces[s], slots[sel], x0[sel], z0[sel])
@@ -1338,7 +1435,8 @@ def main():
 
     # device addresses of each tick's batch, taken once (torch row views cost microseconds of host time
     # per call, during which the GPU would sit idle between ticks)
-    row_ptrs = [(d_slots[t].data_ptr(), d_x[t].data_ptr(), d_z[t].data_ptr()) for t in range(ticks)]
+    batch_ptrs = [(d_slots[k].data_ptr(), d_x[k].data_ptr(), d_z[k].data_ptr()) for k in range(n_batches)]
+    row_ptrs = [batch_ptrs[k] for k in which]
 
     tick_counts = {}  # (enters, leaves) per tick: the claims sub-record must match them
 
@@ -1418,6 +1516,15 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's events are still in HBM (nothing has flushed since): what its caller got
+        d_ent, d_lev = w.events_device()
+        ne, nl = tick_counts[timed_end - 1]
+        counts = np.array([tick_counts[t] for t in range(args.warmup, timed_end)], np.uint64).reshape(-1, 2)
+        dumped = dump_outputs(args.dump_outputs, {"enter_pairs": device_pairs(d_ent, ne),
+                                                  "leave_pairs": device_pairs(d_lev, nl), "event_counts": counts})
 
     timed_stages = w.stage_times() if not args.no_timing else {}
     info = w.info()
@@ -1523,6 +1630,10 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic (seeded SplitMix64, generated on host, resident in HBM before timing)",
+            "full": args.full,
+            "move_batches": {"distinct": n_batches, "ticks": ticks,
+                             "note": "tick t applies batch batch_index(t): forwards, then backwards, and so on"},
+            "dumped_outputs": dumped,
             "config": {"workload": f"{args.workload}: {WORKLOAD_DESC[args.workload]}", "entities_per_rank": n,
                        "spaces_per_rank": wl.n_spaces, "aoi_distance": float(wl.D),
                        "parallelism": (f"spaces sharded over {ws} ranks, contiguous blocks balanced by entity count"

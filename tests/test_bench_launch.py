@@ -69,6 +69,46 @@ def test_line_summary_is_last_and_compact():
     assert len(__import__("json").dumps(s)) < 1200
 
 
+def test_batch_index_walks_forwards_then_backwards():
+    """Up to n_batches ticks use their own batch; later ticks only ever step to a neighbouring batch."""
+    assert [bench.batch_index(t, 4) for t in range(10)] == [0, 1, 2, 3, 2, 1, 0, 1, 2, 3]
+    assert [bench.batch_index(t, 1) for t in range(3)] == [0, 0, 0]
+    idx = [bench.batch_index(t, bench.MAX_BATCHES) for t in range(5 * bench.MAX_BATCHES)]
+    assert idx[:bench.MAX_BATCHES] == list(range(bench.MAX_BATCHES))
+    assert all(abs(a - b) == 1 for a, b in zip(idx, idx[1:]))
+
+
+@pytest.mark.parametrize("cfg,n", [("cfg3", 5001), ("cfg2", 1000)])
+def test_generate_batches_equals_workload_ticks(cfg, n):
+    """The threaded generator gives Workload.tick's batches bit for bit and leaves the workload where
+    the ticks would."""
+    import numpy as np
+    from goworld_amd.workload import make_workload
+    a, b = make_workload(cfg, n=n, seed=0x5EED0003), make_workload(cfg, n=n, seed=0x5EED0003)
+    want = [a.tick(t) for t in range(5)]
+    got = bench.generate_batches(b, range(5), threads=3)
+    for w, g in zip(want, got):
+        for x, y in zip(w, g):
+            assert x.dtype == y.dtype and np.array_equal(x.view(np.uint32), y.view(np.uint32))
+    assert np.array_equal(a.x.view(np.uint32), b.x.view(np.uint32))
+    assert np.array_equal(a.z.view(np.uint32), b.z.view(np.uint32))
+
+
+def test_dump_outputs_float64_and_bounded(tmp_path, monkeypatch):
+    import numpy as np
+    pairs = np.arange(2000, dtype=np.uint32).reshape(-1, 2)
+    rows = bench.dump_outputs(str(tmp_path / "d"), {"pairs": pairs, "counts": np.array([[3, 4]], np.uint64)})
+    got = np.load(tmp_path / "d" / "pairs.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, pairs) and rows == {"pairs": [1000, 1000], "counts": [1, 1]}
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 16 * 100)  # 100 rows of two float64 per array
+    rows = bench.dump_outputs(str(tmp_path / "e"), {"pairs": pairs, "counts": np.array([[3, 4]], np.uint64)})
+    cut = np.load(tmp_path / "e" / "pairs.npy")
+    assert rows["pairs"] == [100, 1000] and cut.shape == (100, 2)
+    assert np.all(np.diff(cut[:, 0]) > 0) and np.all(cut[:, 1] == cut[:, 0] + 1)  # whole rows, in order
+    again = bench.dump_outputs(str(tmp_path / "f"), {"pairs": pairs, "counts": np.array([[3, 4]], np.uint64)})
+    assert again == rows and np.array_equal(np.load(tmp_path / "f" / "pairs.npy"), cut)  # the same sample every run
+
+
 def test_cpu_core_counts_bounded_by_affinity():
     c = bench.cpu_core_counts()
     assert 1 <= c["used"] <= c["affinity"]

@@ -119,7 +119,7 @@ def main():
     with open(dst + ".json", "w") as fh:
         json.dump(js, fh, indent=1)
     lines = [f"# rocprofv3 summary ({os.path.basename(dst)})", "",
-             "Command: `tools/profile.sh` = `rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 8 --warmup 2`, "
+             "Command: `tools/profile.sh` = `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 8 --warmup 2`, "
              "then separate `--pmc` passes (SQ block with SQ_WAIT_ANY / SQ_ACTIVE_INST_ANY, TCP/TCC hit counters, FETCH_SIZE, WRITE_SIZE). "
              "PMC values are medians over steady-state dispatches; read bytes = 32/64/128 B x TCC_EA0_RDREQ_{32B,64B,128B} "
              "when that pass ran (else 2 x FETCH_SIZE, the gfx950 factor for 128-B streaming requests).", ""]

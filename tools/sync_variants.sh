@@ -4,6 +4,6 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for v in "$@"; do
   if [ "$v" = base ]; then L=""; else L=$R/goworld_amd/lib/variants/$v.so; fi
-  GWAOI_LIB=$L timeout -k 10 200 python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --cfg4-steps 0 --host-tick-steps 0 --host-io-steps 0 --breakdown-steps 0 --sync-steps 8 > /tmp/sv.json 2>/tmp/sv.err || { echo "$v failed"; tail -5 /tmp/sv.err; exit 1; }
+  GWAOI_LIB=$L timeout -k 10 200 python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --cfg4-steps 0 --host-tick-steps 0 --host-io-steps 0 --breakdown-steps 0 --sync-steps 8 > /tmp/sv.json 2>/tmp/sv.err || { echo "$v failed"; tail -5 /tmp/sv.err; exit 1; }
   python3 -c "import json;d=json.load(open('/tmp/sv.json'));s=d['sync_leg'];print('$v', round(d['ms_per_step'],4), 'decode_flush', round(s['decode_flush_ms'],4), 'collect', round(s['collect_ms'],4))"
 done

@@ -28,7 +28,7 @@ def main():
             env = dict(os.environ)
             if name != "base":
                 env["GWAOI_LIB"] = os.path.join(VDIR, name + ".so")
-            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline",
+            r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline",
                                 "--host-io-steps", "0", "--sync-steps", "0", "--cfg4-steps", "0",
                                 "--host-tick-steps", "0", "--wire-steps", "0", "--cfg5-steps", "0", "--small-flush-reps", "0",
                                 "--claims-steps", "0", *bargs],
