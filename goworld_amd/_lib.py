@@ -69,7 +69,7 @@ SYNC_EXPORTS = [
     "gwaoi_entity_set_syncing", "gwaoi_entity_set_position_yaw", "gwaoi_set_position_yaw",
     "gwaoi_sync_from_clients", "gwaoi_sync_from_clients_device", "gwaoi_collect_sync_infos",
     "gwaoi_collect_sync_infos_device", "gwaoi_collect_client_events", "gwaoi_entity_enter_plain",
-    "gwaoi_entity_leave_plain",
+    "gwaoi_entity_leave_plain", "gwaoi_collect_broadcast", "gwaoi_collect_broadcast_device",
 ]
 
 # every function include/gwaoi_wire.h declares
@@ -83,6 +83,9 @@ WIRE_EXPORTS = [
 SYNC_OUT_REC = 48  # ClientID[16] + EntityID[16] + x,y,z,yaw float32 (Entity.go:1233-1251)
 DESTROY_REC = 32   # ClientID[16] + EntityID[16]
 SIF_OWN_CLIENT, SIF_NEIGHBOR_CLIENTS = 1, 2
+CAST_REC = 32      # ClientID[16] + msg, src slot, dst slot, 0 (uint32 little-endian): gwaoi_collect_broadcast
+CAST_OWN, CAST_NEIGHBORS = 1, 2
+CAST_DTYPE = np.dtype([("cid", np.uint8, (16,)), ("msg", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("pad", "<u4")])
 
 
 class Config(C.Structure):
@@ -229,6 +232,8 @@ def load():
         "gwaoi_collect_sync_infos": ([vp, P(GateRecords)], C.c_int),
         "gwaoi_collect_sync_infos_device": ([vp, P(GateRecords)], C.c_int),
         "gwaoi_collect_client_events": ([vp, P(GateRecords), P(GateRecords)], C.c_int),
+        "gwaoi_collect_broadcast": ([vp, vp, vp, sz, P(GateRecords)], C.c_int),
+        "gwaoi_collect_broadcast_device": ([vp, vp, vp, sz, P(GateRecords)], C.c_int),
         "gwaoi_wire_create": ([C.c_int, P(vp)], C.c_int),
         "gwaoi_wire_destroy": ([vp], None),
         "gwaoi_wire_last_error": ([vp], C.c_char_p),
@@ -656,6 +661,32 @@ class World:
         c, d = GateRecords(), GateRecords()
         self._check(self._L.gwaoi_collect_client_events(self._w, C.byref(c), C.byref(d)))
         return _gate_dict(c, SYNC_OUT_REC), _gate_dict(d, DESTROY_REC)
+
+    def collect_broadcast(self, slots, flags=None) -> dict:
+        """AllClients delivery of a batch of messages (gwaoi_collect_broadcast): message m comes
+        from entity slots[m] with flags[m] (CAST_OWN | CAST_NEIGHBORS; None: both for every
+        message).  Returns {gate_id: (n,32) uint8 records} of the gates that receive any (an empty
+        batch gives {}); view a gate's array as CAST_DTYPE."""
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.uint32).reshape(-1)
+        f = None
+        if flags is not None:
+            f = np.ascontiguousarray(np.atleast_1d(flags), np.uint32).reshape(-1)
+            if f.size != s.size:
+                raise ValueError(f"{s.size} slots but {f.size} flags")
+        g = GateRecords()
+        self._check(self._L.gwaoi_collect_broadcast(self._w, _p(s) if s.size else None,
+                                                    _p(f) if f is not None and f.size else None, s.size, C.byref(g)))
+        return {k: a for k, a in _gate_dict(g, CAST_REC).items() if len(a)}
+
+    def collect_broadcast_device(self, d_slots: int, d_flags: int, n: int):
+        """Messages in device memory (d_flags 0: both flags for every message), records stay in
+        HBM: (gate_ids, offsets (records), device pointer), valid until the next broadcast."""
+        g = GateRecords()
+        self._check(self._L.gwaoi_collect_broadcast_device(self._w, C.c_void_p(d_slots) if d_slots else None,
+                                                           C.c_void_p(d_flags) if d_flags else None, n, C.byref(g)))
+        ids = [g.gate_ids[i] for i in range(g.n_gates)]
+        off = [g.offsets[i] for i in range(g.n_gates + 1)] if g.n_gates else [0]
+        return ids, off, g.records or 0
 
 
 def _ids(ids, n) -> np.ndarray:

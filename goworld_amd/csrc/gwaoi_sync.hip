@@ -1,6 +1,6 @@
 // gwaoi_sync.hip -- entity position sync around the AOI path (include/gwaoi_sync.h).
 //
-// Three device passes, all on the world's stream:
+// Four device passes, all on the world's stream:
 //   decode    HandleSyncPositionYawFromClient (GameService.go:392-404): one
 //             lane per 32-B record, entity-id hash lookup, the record becomes
 //             op i of a device Moved batch (SLOT_NONE = skipped), Y/yaw by
@@ -12,6 +12,10 @@
 //   route     Entity.interest/uninterest -> sendCreateEntity/sendDestroyEntity
 //             (Entity.go:236-246, GameClient.go:37-59): the flush's events
 //             whose first entity has a client, grouped by gate.
+//   broadcast Entity.CallAllClients / ForAllClients / send*AttrChange...ToClients
+//             (Entity.go:743-917), source side: one wave per (source, flags)
+//             message; a record for the source's own client and one per B with
+//             rel(source, B) that has a client, grouped by gate.
 // Grouping by gate is a multisplit: a first pass counts records per
 // (gate, block) in LDS, an exclusive scan gives every (gate, block) its
 // base, a second pass writes each block's runs (the fan-out's first pass
@@ -833,6 +837,178 @@ __global__ __launch_bounds__(ST) void k_fan_write(FanArgs A) {
     }
 }
 
+// ---------------------------------------------------------- broadcast ------
+// Source side: GoWorld's AllClients delivery (Entity.CallAllClients, ForAllClients and the
+// sendMapAttr* / sendListAttr* ...ToClients functions, Entity.go:743-917) for a sparse batch of
+// messages.  Message m = (source slot, flags) yields one 32-B record {ClientID, m, source slot,
+// receiver slot, 0} for the source's own client (GWAOI_CAST_OWN) and one for the client of
+// every B with rel(source, B) (GWAOI_CAST_NEIGHBORS: B in the source's InterestedBy), grouped
+// by the receiver's gate.  One wave per message; a block takes a contiguous chunk of messages,
+// its waves every fourth one.  The source's window is walked twice and no hit list is kept:
+// k_cast_count counts the block's records per gate in LDS, the scan gives every (gate, block)
+// its base, k_cast_write repeats the walk (one body, cast_pass) and a hit takes the next
+// position of its gate's run from an LDS cursor.  The walk is k_fan_hits_wave's: lane j loads
+// row j's bounds, the rows are laid end to end and the wave reads 64 consecutive candidates
+// per step; only hits go on to the candidate's slot and the first 16 B of its slot record
+// (the gate), the other lanes re-read the source's (clamped index: no load under a per-lane
+// branch).  Nothing is written but the counts and the output.
+constexpr int CAST_WU = 2;  // steps of 64 candidates with their loads in flight together
+constexpr uint32_t CAST_MAX_BLOCKS = 2048;  // the [G][nb] count table: 8 MB at 1,024 gates
+constexpr unsigned long long CAST_E_SLOT = 1ull << 62;   // device form: a message's slot >= max_slots
+constexpr unsigned long long CAST_E_FLAGS = 1ull << 63;  // device form: a flag bit outside OWN | NEIGHBORS
+constexpr unsigned long long CAST_TOTAL = CAST_E_SLOT - 1ull;
+
+struct CastArgs {
+    FrameView F;
+    SlotTab info;
+    const uint4 *slots;       // SLOT_U4 per slot: sst, pos, eid, cid
+    const uint32_t *m_slot;   // the messages' source slots
+    const uint32_t *m_flags;  // their flags (nullptr: OWN | NEIGHBORS for every message)
+    uint32_t n, max_slots;
+    uint32_t G, nb, per;  // gates, blocks, messages per block
+    uint32_t *blk_cnt;    // [G][nb] (the count pass writes, the scan turns it into bases)
+    unsigned long long *sc;  // records of all blocks (64-bit: the scan's total wraps) | CAST_E_*
+    uint4 *out;              // 2 uint4 per record (write pass)
+    unsigned long long out_recs;  // records out holds (the write pass writes nothing past a larger total)
+};
+
+__device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+template <bool WRITE>
+__device__ __forceinline__ void cast_pass(const CastArgs &A) {
+    extern __shared__ uint32_t gcur[];  // [G] count: the block's records per gate; write: next position of its run
+    __shared__ uint32_t s_adj[ST / 64][64];             // candidate index - position, per non-empty row
+    __shared__ uint32_t s_mark[ST / 64][CAST_WU * 64];  // a non-empty row starts at this position
+    __shared__ unsigned long long s_tot;
+    // queued behind the count pass without a host round trip: nothing to do when the total outgrew
+    // the output (the host sees it after its one sync, regrows and relaunches)
+    if (WRITE && (*A.sc & CAST_TOTAL) > A.out_recs) return;
+    const uint32_t blk = blockIdx.x, w = threadIdx.x / 64, ln = s_lane();
+    for (uint32_t q = threadIdx.x; q < A.G; q += blockDim.x) gcur[q] = WRITE ? A.blk_cnt[(size_t)q * A.nb + blk] : 0u;
+    if (!WRITE && threadIdx.x == 0) s_tot = 0ull;
+    __syncthreads();
+    const uint32_t *cs = A.F.cell_start;
+    const uint4 *frec = reinterpret_cast<const uint4 *>(A.F.rec);
+    const unsigned long long lt = (1ull << ln) - 1ull;
+    const unsigned long long le = ln == 63 ? ~0ull : (2ull << ln) - 1ull;
+    unsigned long long wtot = 0ull, werr = 0ull;  // (wave-uniform)
+    const uint32_t m1 = min(A.n, (blk + 1u) * A.per);
+    for (uint32_t m = blk * A.per + w; m < m1; m += ST / 64) {
+        const uint32_t slot = rfl(A.m_slot[m]);
+        const uint32_t fl = A.m_flags ? rfl(A.m_flags[m]) : (GWAOI_CAST_OWN | GWAOI_CAST_NEIGHBORS);
+        if (slot >= A.max_slots) {  // (device form only: the host form is checked on the host)
+            werr |= CAST_E_SLOT;
+            continue;
+        }
+        if (fl & ~(GWAOI_CAST_OWN | GWAOI_CAST_NEIGHBORS)) {
+            werr |= CAST_E_FLAGS;
+            continue;
+        }
+        if (!fl) continue;
+        // the source: its frame index, gate and (write pass) ClientID in one round trip
+        const uint32_t r0 = rfl(A.info.rank[slot]);
+        const uint4 st0 = A.slots[SLOT_U4 * (size_t)slot];
+        uint4 ci0 = make_uint4(0, 0, 0, 0);
+        if (WRITE) ci0 = A.slots[SLOT_U4 * (size_t)slot + 3];
+        // one record: its gate's count, or the next position of its gate's run and the two stores
+        auto emit = [&](bool v, uint32_t g, uint32_t dst, const uint4 &cid) {
+            v = v && g < A.G;  // (NO_GATE: no client)
+            if (v) {
+                const uint32_t p = atomicAdd(&gcur[g], 1u);
+                if (WRITE && p < A.out_recs) {
+                    A.out[2 * (size_t)p] = cid;
+                    A.out[2 * (size_t)p + 1] = make_uint4(m, slot, dst, 0u);
+                }
+            }
+            if (!WRITE) wtot += (unsigned long long)__popcll(__ballot(v));
+        };
+        // the own client's record whether or not the source is in an AOI space (e.client is
+        // independent of the space; GameClient's methods are no-ops on a nil client)
+        emit(ln == 0 && (fl & GWAOI_CAST_OWN), st0.x, slot, ci0);
+        if (!(fl & GWAOI_CAST_NEIGHBORS) || r0 >= A.F.n) continue;  // (rank: 0xFFFFFFFF if never live)
+        const SlotSp S0 = ld_ss(A.F.ss, r0);
+        const Rec16 R = ld_rec(A.F.rec, r0);
+        if (rfl(S0.slot) != slot) continue;  // left the frame: nilSpace or a space without AOI, no neighbours
+        // the source's go-aoi window (cells), exactly fan_window's: the same float32 margin, in
+        // the source's own space grid
+        const SpaceGrid gr = A.F.grid[rfl(S0.sp)];
+        const float D = gr.D;
+        const float mx = (fabsf(R.x) + 3.0f * D) * 0x1p-20f, mz = (fabsf(R.z) + 3.0f * D) * 0x1p-20f;
+        const int cx0 = cell_of(R.x - D - mx, gr.ox, gr.inv, gr.gx), cx1 = cell_of(R.x + D + mx, gr.ox, gr.inv, gr.gx);
+        const int cz0 = cell_of(R.z - D - mz, gr.oz, gr.inv, gr.gz), cz1 = cell_of(R.z + D + mz, gr.oz, gr.inv, gr.gz);
+        const uint32_t span = rfl((uint32_t)(cx1 - cx0) + 1u), nrows = rfl((uint32_t)(cz1 - cz0) + 1u);
+        const uint32_t row0 = rfl(gr.base + (uint32_t)cz0 * gr.gx + (uint32_t)cx0), gx = rfl(gr.gx);
+        for (uint32_t j0 = 0; j0 < nrows; j0 += 64u) {
+            // lane t: row j0 + t of the window, its candidates [jb, je)
+            const uint32_t t = j0 + ln;
+            const uint32_t rb = row0 + min(t, nrows - 1u) * gx;
+            const uint32_t jb = cs[rb], je = cs[rb + span];
+            const uint32_t len = t < nrows ? je - jb : 0u;
+            const uint32_t incl = wave_scan_add(len);
+            const uint32_t ex = incl - len, T = rdl(incl, 63);
+            const unsigned long long nem = __ballot(len != 0u);
+            if (len) s_adj[w][__popcll(nem & lt)] = jb - ex;
+            for (uint32_t p0 = 0; p0 < T; p0 += CAST_WU * 64u) {
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) s_mark[w][u * 64 + ln] = 0u;
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                if (len && ex >= p0 && ex - p0 < CAST_WU * 64u) s_mark[w][ex - p0] = 1u;
+                uint32_t nr = (uint32_t)__popcll(__ballot(len != 0u && ex < p0));  // non-empty rows started before this step
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                uint32_t b[CAST_WU];
+                uint4 q[CAST_WU];
+                bool hit[CAST_WU];
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) {
+                    const unsigned long long mk = __ballot(s_mark[w][u * 64 + ln] != 0u);
+                    const uint32_t p = p0 + (uint32_t)u * 64u + ln;
+                    const uint32_t row = nr + (uint32_t)__popcll(mk & le);  // rows started at or before p
+                    nr += (uint32_t)__popcll(mk);
+                    b[u] = p < T ? p + s_adj[w][row - 1u] : r0;  // (row >= 1 whenever p < T)
+                    q[u] = frec[b[u]];
+                }
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) {
+                    const uint32_t p = p0 + (uint32_t)u * 64u + ln;
+                    const unsigned long long bs = ((unsigned long long)q[u].w << 32) | q[u].z;
+                    hit[u] = p < T && b[u] != r0 &&  // (the source is never its own neighbour)
+                             rel(R.x, R.z, R.s, __uint_as_float(q[u].x), __uint_as_float(q[u].y), bs, D);
+                }
+                // the hits' receivers: slot, then gate (and ClientID), every lane's load issued
+                // (a lane without a hit re-reads the source's)
+                uint32_t ds[CAST_WU];
+                uint4 st[CAST_WU], ci[CAST_WU];
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) ds[u] = ld_ss(A.F.ss, hit[u] ? b[u] : r0).slot;
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) {
+                    st[u] = A.slots[SLOT_U4 * (size_t)ds[u]];
+                    ci[u] = make_uint4(0, 0, 0, 0);
+                    if (WRITE) ci[u] = A.slots[SLOT_U4 * (size_t)ds[u] + 3];
+                }
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) emit(hit[u], st[u].x, ds[u], ci[u]);
+            }
+            __builtin_amdgcn_wave_barrier();  // s_adj is rewritten by the next row group
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        }
+    }
+    if (WRITE) return;
+    if (ln == 0 && wtot) atomicAdd(&s_tot, wtot);
+    if (ln == 0 && werr) atomicOr(A.sc, werr);  // (one lane per wave that saw a bad message)
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < A.G; q += blockDim.x) A.blk_cnt[(size_t)q * A.nb + blk] = gcur[q];
+    if (threadIdx.x == 0) {
+        if (s_tot) atomicAdd(A.sc, s_tot);  // one per block
+        if (blk == 0) A.blk_cnt[(size_t)A.G * A.nb] = 0u;  // the scan's last entry becomes the (32-bit) total
+    }
+}
+
+__global__ __launch_bounds__(ST) void k_cast_count(CastArgs A) { cast_pass<false>(A); }
+__global__ __launch_bounds__(ST) void k_cast_write(CastArgs A) { cast_pass<true>(A); }
+
 // -------------------------------------------------------------- route ------
 struct RouteArgs {
     const uint32_t *ev;  // (a,b) pairs: [enters | leaves]
@@ -968,6 +1144,16 @@ struct SyncState {
     std::vector<uint64_t> h_off, h_off_c, h_off_d;
     uint8_t *h_rec = nullptr, *h_rec_d = nullptr;
     size_t h_rec_cap = 0, h_recd_cap = 0;
+    // broadcast collect: the host form's uploaded messages, the total / error word, and outputs
+    // of its own (valid until the next broadcast collect, whatever the other collects do)
+    uint32_t *cast_in = nullptr;
+    size_t cast_in_cap = 0;
+    unsigned long long *cast_sc = nullptr;
+    uint4 *cast_out = nullptr;
+    size_t cast_out_cap = 0;  // in uint4
+    uint8_t *h_cast = nullptr;
+    size_t h_cast_cap = 0;
+    std::vector<uint64_t> h_off_cast;
 };
 
 namespace {
@@ -1453,6 +1639,100 @@ int collect_sync(gwaoi_world *w, gwaoi_gate_records *out, bool to_host) {
     return GWAOI_OK;
 }
 
+// gwaoi_collect_broadcast(_device): messages (slots[m], flags[m]) in host or device memory.
+// Reads the state of the last flush and changes none of it.
+int collect_cast(gwaoi_world *w, const uint32_t *slots, const uint32_t *flags, size_t n, gwaoi_gate_records *out,
+                 bool on_device) {
+    if (!w || !out || (n && !slots)) return GWAOI_EINVAL;
+    SyncState *S;
+    if (int rc = state(w, &S)) return rc;
+    const WorldView v = world_view(w);
+    if (v.pending_ops) return GWAOI_ESTATE;
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    if (!on_device)  // nothing is produced on error: checked before any device work
+        for (size_t m = 0; m < n; ++m) {
+            if (flags && (flags[m] & ~(GWAOI_CAST_OWN | GWAOI_CAST_NEIGHBORS))) return GWAOI_EINVAL;
+            if (slots[m] >= S->max_slots) return GWAOI_EBADSLOT;
+        }
+    if (int rc = push(S)) return rc;
+    const uint32_t G = (uint32_t)S->gate_ids.size();
+    S->h_off_cast.assign((size_t)G + 1, 0);
+    uint64_t total = 0;
+    int status = GWAOI_OK;
+    if (G && n) {
+        CastArgs A{};
+        A.F = v.F;
+        A.info = v.info;
+        A.slots = S->slots;
+        if (on_device) {
+            A.m_slot = slots;
+            A.m_flags = flags;
+        } else {
+            if (int rc = ensure_u32(S, &S->cast_in, &S->cast_in_cap, 2 * n)) return rc;
+            SY_TRY(hipMemcpyAsync(S->cast_in, slots, n * 4, hipMemcpyHostToDevice, S->st));
+            if (flags) SY_TRY(hipMemcpyAsync(S->cast_in + n, flags, n * 4, hipMemcpyHostToDevice, S->st));
+            A.m_slot = S->cast_in;
+            A.m_flags = flags ? S->cast_in + n : nullptr;
+        }
+        A.n = (uint32_t)n;
+        A.max_slots = S->max_slots;
+        // a block loops over a contiguous chunk of messages, its waves every (ST / 64)-th one; the
+        // grid is capped so that the [G][nb] table stays bounded.  Both passes take these.
+        A.per = std::max<uint32_t>(ST / 64, (cdivu(n, CAST_MAX_BLOCKS) + ST / 64 - 1) / (ST / 64) * (ST / 64));
+        A.nb = cdivu(n, A.per);
+        A.G = G;
+        if (int rc = ensure_u32(S, &S->blk_cnt, &S->blk_cap, (size_t)G * A.nb + 1)) return rc;
+        A.blk_cnt = S->blk_cnt;
+        if (!S->cast_sc)
+            if (int rc = salloc(S, &S->cast_sc, 1)) return rc;
+        A.sc = S->cast_sc;
+        SY_TRY(hipMemsetAsync(S->cast_sc, 0, 8, S->st));
+        k_cast_count<<<A.nb, ST, (size_t)G * 4, S->st>>>(A);
+        SY_TRY(hipGetLastError());
+        // as the fan-out: the bases are scanned and the write pass queued with the output as it
+        // is (the last broadcast's size) before the one host wait, which brings the per-gate
+        // bases, the 64-bit total and the device form's error bits
+        if (int rc = part_bases(S, G, A.nb, false, false, S->cast_sc)) return rc;
+        A.out = S->cast_out;
+        A.out_recs = S->cast_out_cap / 2;
+        if (A.out_recs) {
+            k_cast_write<<<A.nb, ST, (size_t)G * 4, S->st>>>(A);
+            SY_TRY(hipGetLastError());
+        }
+        if (int rc = fetch_bases(S, G, false)) return rc;
+        SY_TRY(hipStreamSynchronize(S->st));
+        const unsigned long long sc = unpack_bases(S, G);
+        if (sc & CAST_E_FLAGS) status = GWAOI_EINVAL;
+        if (sc & CAST_E_SLOT) status = GWAOI_EBADSLOT;
+        total = sc & CAST_TOTAL;
+        if (total > 0xFFFFFFFFull) {
+            world_set_error(w, "sync: a broadcast of more than 2^32 - 1 records");
+            return GWAOI_ECAPACITY;
+        }
+        if (total > A.out_recs) {  // (first broadcast, or more records than the output holds)
+            if (int rc = ensure_out(S, &S->cast_out, &S->cast_out_cap, 2 * total)) return rc;
+            A.out = S->cast_out;
+            A.out_recs = S->cast_out_cap / 2;
+            k_cast_write<<<A.nb, ST, (size_t)G * 4, S->st>>>(A);
+            SY_TRY(hipGetLastError());
+        }
+        S->h_off_cast.assign(S->h_off_raw.begin(), S->h_off_raw.end());
+    }
+    if (int rc = ensure_out(S, &S->cast_out, &S->cast_out_cap, 2)) return rc;  // (an empty result's pointer)
+    if (!on_device) {
+        if (int rc = ensure_host(S, &S->h_cast, &S->h_cast_cap, std::max<uint64_t>(total, 1) * GWAOI_CAST_REC)) return rc;
+        if (total)
+            SY_TRY(hipMemcpyAsync(S->h_cast, S->cast_out, total * GWAOI_CAST_REC, hipMemcpyDeviceToHost, S->st));
+        SY_TRY(hipStreamSynchronize(S->st));
+        fill_out(S, out, S->h_off_cast, S->h_cast);
+    } else {
+        SY_TRY(hipStreamSynchronize(S->st));  // (the caller's arrays are free to go; the records are complete)
+        fill_out(S, out, S->h_off_cast, reinterpret_cast<const uint8_t *>(S->cast_out));
+    }
+    if (status != GWAOI_OK) world_set_error(w, "sync: broadcast messages with a bad slot or flag were dropped");
+    return status;
+}
+
 int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
     if (!w || (n && !payload)) return GWAOI_EINVAL;
     if (on_device && (reinterpret_cast<uintptr_t>(payload) & 15u)) return GWAOI_EINVAL;
@@ -1560,6 +1840,8 @@ void sync_destroy(SyncState *S) {
     sfree(S->f_snd); sfree(S->f_rg); sfree(S->f_rec); sfree(S->f_frec); sfree(S->f_cid);
     sfree(S->blk_cnt); sfree(S->scan_tmp); sfree(S->scr); sfree(S->scr_cursor); sfree(S->f_cnt); sfree(S->f_sb); sfree(S->d_off); sfree(S->d_left); sfree(S->out); sfree(S->out_d);
     sfree(S->d_stage);
+    sfree(S->cast_in); sfree(S->cast_sc); sfree(S->cast_out);
+    if (S->h_cast) (void)hipHostFree(S->h_cast);
     for (auto &c : S->arena) (void)hipFree(c.p);
     if (S->h_stage) (void)hipHostFree(S->h_stage);
     if (S->h_rec) (void)hipHostFree(S->h_rec);
@@ -1734,6 +2016,20 @@ int gwaoi_collect_sync_infos(gwaoi_world *w, gwaoi_gate_records *out) { return g
 int gwaoi_collect_sync_infos_device(gwaoi_world *w, gwaoi_gate_records *out) {
     return gw::api_guard([&]() -> int {
     return gw::collect_sync(w, out, false);
+    });
+}
+
+int gwaoi_collect_broadcast(gwaoi_world *w, const uint32_t *slots, const uint32_t *flags, size_t n,
+                            gwaoi_gate_records *out) {
+    return gw::api_guard([&]() -> int {
+    return gw::collect_cast(w, slots, flags, n, out, false);
+    });
+}
+
+int gwaoi_collect_broadcast_device(gwaoi_world *w, const uint32_t *d_slots, const uint32_t *d_flags, size_t n,
+                                   gwaoi_gate_records *out) {
+    return gw::api_guard([&]() -> int {
+    return gw::collect_cast(w, d_slots, d_flags, n, out, true);
     });
 }
 

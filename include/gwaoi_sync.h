@@ -19,6 +19,12 @@
  *      ClientID[16] + EntityID[16] + x,y,z,yaw float32)
  *   Entity.interest / uninterest -> GameClient.sendCreateEntity / sendDestroyEntity
  *     Entity.go:236-246, GameClient.go:37-59                    gwaoi_collect_client_events
+ *   Entity.CallAllClients               Entity.go:743-749       gwaoi_collect_broadcast(_device)
+ *   Entity.ForAllClients                Entity.go:768-778         (the own client plus the client of
+ *   Entity.sendMapAttrChangeToClients / sendMapAttrDelToClients /  every entity in InterestedBy; the
+ *     sendMapAttrClearToClients / sendListAttrChangeToClients /    caller attaches the RPC or
+ *     sendListAttrPopToClients / sendListAttrAppendToClients       attribute payload per record)
+ *     for AllClients attributes         Entity.go:814-917
  *
  * Entity ids and client ids are the reference's 16-byte strings
  * (common.ENTITYID_LENGTH = common.CLIENTID_LENGTH = uuid.UUID_LENGTH = 16,
@@ -132,6 +138,50 @@ int gwaoi_collect_sync_infos_device(gwaoi_world *w, gwaoi_gate_records *out);
  * caller adds type name and client data per record (GameClient.go:37-53).
  * Host memory. */
 int gwaoi_collect_client_events(gwaoi_world *w, gwaoi_gate_records *creates, gwaoi_gate_records *destroys);
+
+/* ---- broadcast ------------------------------------------------------------ */
+#define GWAOI_CAST_REC 32        /* ClientID[16] | msg u32 | src slot u32 | dst slot u32 | 0 u32, little-endian */
+#define GWAOI_CAST_OWN 1u        /* the source's own client (e.client.call / sendNotify*)          */
+#define GWAOI_CAST_NEIGHBORS 2u  /* the client of every entity in the source's InterestedBy         */
+
+/* AllClients delivery (CallAllClients, ForAllClients and the AllClients
+ * attribute notifications, Entity.go:743-917) of a batch of n messages:
+ * per-gate lists of (receiving ClientID, message index).
+ *
+ * Messages.  Message m is entry m of the arrays; `msg` of a record is m, so
+ * the caller attaches the payload.  flags == NULL means OWN | NEIGHBORS for
+ * every message.  A slot may appear any number of times: each message fans
+ * out on its own.  flags[m] == 0 yields nothing.
+ * Relation.  The go-aoi relation of the last committed flush, the one
+ * gwaoi_neighbors and gwaoi_collect_sync_infos read: GWAOI_ESTATE with ops
+ * queued or a flush in flight, as for the collects.
+ * Records.  An OWN record has dst == src and is emitted if the source has a
+ * client, whether or not the source is in an AOI space.  A NEIGHBORS record
+ * is emitted for each b with rel(src, b) (b in src's InterestedBy) that has a
+ * client: dst is b's slot and the record goes to b's gate.  The source never
+ * appears as its own neighbour.  (GameClient's methods are no-ops on a nil
+ * client, GameClient.go:61-106: entities without a client get nothing.)
+ * Sources outside any AOI frame (nilSpace, a space without AOI, a slot never
+ * bound or entered) have no neighbours: only the OWN record can result.
+ * State.  The call changes nothing: sync flags, positions and the relation
+ * are untouched, and calling it twice gives the same multiset.  Records of
+ * one gate come in an unspecified order; the multiset per gate is exact.
+ * Output.  `out` is filled as for the other collects, with buffers of its
+ * own: valid until the next broadcast collect.  n == 0 or no client anywhere
+ * gives an empty result and GWAOI_OK; more than 2^32 - 1 records give
+ * GWAOI_ECAPACITY.
+ * Errors, host form (nothing is produced): null w, out, or slots with n > 0:
+ * GWAOI_EINVAL; a flag bit outside OWN | NEIGHBORS: GWAOI_EINVAL; a slot >=
+ * max_slots: GWAOI_EBADSLOT.
+ * Errors, device form (d_slots / d_flags in device memory of the world's GPU,
+ * read before the call returns): an offending message is dropped, the others
+ * are delivered in *out, and the call returns GWAOI_EBADSLOT / GWAOI_EINVAL,
+ * as the device Moved batches report; the world stays usable. */
+int gwaoi_collect_broadcast(gwaoi_world *w, const uint32_t *slots, const uint32_t *flags, size_t n,
+                            gwaoi_gate_records *out);
+/* Same; messages in device memory, records stay in device memory. */
+int gwaoi_collect_broadcast_device(gwaoi_world *w, const uint32_t *d_slots, const uint32_t *d_flags, size_t n,
+                                   gwaoi_gate_records *out);
 
 #ifdef __cplusplus
 }
