@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libgwaoi.so")
 SOURCES = ["gwaoi_kernels.hip", "gwaoi_world.cpp", "gwaoi_strips.hip", "gwaoi_sync.hip", "gwaoi_wire.hip",
            "gwaoi_sparse.hip"]
-HEADERS = ["gwaoi_internal.h", "gwaoi_device.h", os.path.join("..", "..", "include", "gwaoi.h"),
+HEADERS = ["gwaoi_internal.h", "gwaoi_device.h", "gwaoi_mem.h", os.path.join("..", "..", "include", "gwaoi.h"),
            os.path.join("..", "..", "include", "gwaoi_sync.h"),
            os.path.join("..", "..", "include", "gwaoi_strips.h"), os.path.join("..", "..", "include", "gwaoi_wire.h")]
 
@@ -68,7 +68,27 @@ def build_cpp_tests(force: bool = False, verbose: bool = False) -> str:
     return CPP_TEST_OUT
 
 
-TICK_BENCH_SRC = os.path.join(ROOT, "tools", "tick_bench.cpp")
+MEM_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "mem_test.cpp")
+MEM_TEST_OUT = os.path.join(HERE, "lib", "mem_test")
+
+
+def build_mem_test(force: bool = False, verbose: bool = False) -> str:
+    """Stand-alone host test of csrc/gwaoi_mem.h (the owning buffer types): the header and the HIP runtime only."""
+    deps = [MEM_TEST_SRC, os.path.join(CSRC, "gwaoi_mem.h"), os.path.join(ROOT, "include", "gwaoi.h")]
+    if (not force and os.path.exists(MEM_TEST_OUT)
+            and all(os.path.getmtime(d) <= os.path.getmtime(MEM_TEST_OUT) for d in deps)):
+        return MEM_TEST_OUT
+    os.makedirs(os.path.dirname(MEM_TEST_OUT), exist_ok=True)
+    tmp = MEM_TEST_OUT + ".tmp"
+    cmd = [HIPCC, "-std=c++17", "-O1", "-Wall", "-I", CSRC, MEM_TEST_SRC, "-o", tmp]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(tmp, MEM_TEST_OUT)
+    return MEM_TEST_OUT
+
+
+TICK_BENCH_SRC =os.path.join(ROOT, "tools", "tick_bench.cpp")
 TICK_BENCH_OUT = os.path.join(HERE, "lib", "gwaoi_tick_bench")
 
 
@@ -94,3 +114,4 @@ if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
     print(build_cpp_tests(verbose=True))
     print(build_tick_bench(verbose=True))
+    print(build_mem_test(verbose=True))

@@ -25,6 +25,7 @@
 // filter), whose results are then read from pinned memory.
 
 #include "gwaoi_internal.h"
+#include "gwaoi_mem.h"
 #include "../../include/gwaoi_strips.h"
 
 #include <hip/hip_runtime.h>
@@ -547,44 +548,39 @@ struct gwaoi_strips {
     bool broken = false;  // a failed asynchronous tick (complete_or_break)
     std::string broken_msg;
     uint32_t space = 0;
-    hipStream_t st = nullptr;
+    hipStream_t st = nullptr;  // view: the world's stream
     StripGeo geo{};
     uint32_t max_slots = 0;
-    Rec16 *cur = nullptr, *prv = nullptr;
-    uint32_t *ptick = nullptr, *ttick = nullptr;
+    gw::DevBuf<Rec16> cur, prv;
+    gw::DevBuf<uint32_t> ptick, ttick;
     uint32_t tick = 0;
     // multisplit scratch
-    uint32_t *counts = nullptr, *scan_tmp = nullptr, *err = nullptr, *small_d = nullptr;
-    size_t counts_cap = 0, scan_cap = 0;
+    gw::DevBuf<uint32_t> counts, scan_tmp, err, small_d;
     // the filter's own multisplit scratch and the tick's error word: a filter re-run (after the
     // world regrew its events) happens inside the next route, whose counts and error word it
     // must leave alone
-    uint32_t *fcounts = nullptr, *fscan_tmp = nullptr, *terr = nullptr;
-    size_t fcounts_cap = 0, fscan_cap = 0;
-    uint32_t *small_h = nullptr;  // pinned, SM_WORDS
-    int *kstat = nullptr;         // device kind statistics: route (GWAOI_MAX_STRIPS x KS), receive (KS)
+    gw::DevBuf<uint32_t> fcounts, fscan_tmp, terr;
+    gw::PinnedBuf<uint32_t> small_h;  // SM_WORDS
+    gw::DevBuf<int> kstat;            // device kind statistics: route (GWAOI_MAX_STRIPS x KS), receive (KS)
     // route state
     const gwaoi_halo_rec *r_ops = nullptr;
     uint32_t r_n = 0, r_nb = 0;
     bool routed = false;
     bool kinds_valid = false;
     bool row_pending = false;     // gwaoi_strips_route_begin queued, its _end not called yet
-    uint32_t *row_h = nullptr;    // pinned: every strip's count row (gwaoi_strips_route_end)
-    // received records as world ops, SoA [moves | enters | leaves]
-    uint32_t *m_slot = nullptr;
-    float *m_x = nullptr, *m_z = nullptr;
-    unsigned long long *m_seq = nullptr;
-    size_t m_cap = 0;
+    gw::PinnedBuf<uint32_t> row_h;  // every strip's count row (gwaoi_strips_route_end)
+    // received records as world ops, SoA [moves | enters | leaves]: the four grow together
+    // (ensure_moves), m_seq last, so its capacity is the group's
+    gw::DevBuf<uint32_t> m_slot;
+    gw::DevBuf<float> m_x, m_z;
+    gw::DevBuf<unsigned long long> m_seq;
     // teleporter pairs
-    unsigned long long *tcnt = nullptr;
-    uint2 *tpairs = nullptr;
-    size_t tpairs_cap = 0;
+    gw::DevBuf<unsigned long long> tcnt;
+    gw::DevBuf<uint2> tpairs;
     // this strip's events
-    uint2 *out = nullptr;
-    size_t out_cap = 0;
+    gw::DevBuf<uint2> out;
     uint64_t n_enter = 0, n_leave = 0;
-    uint32_t *h_events = nullptr;
-    size_t h_cap = 0;
+    gw::PinnedBuf<uint32_t> h_events;  // two words per event
     // a tick queued by gwaoi_strips_tick_async, completed by the next host wait
     bool pending = false;
     uint64_t pend_tcap = 0;     // its teleporter-pair buffers (for a filter re-run)
@@ -597,65 +593,46 @@ struct gwaoi_strips {
 
 namespace {
 
-#define S_TRY(expr)                                                          \
-    do {                                                                     \
-        hipError_t e_ = (expr);                                              \
-        if (e_ != hipSuccess) {                                              \
-            s->last_error = std::string(#expr) + ": " + hipGetErrorString(e_); \
-            return GWAOI_EDEVICE;                                            \
-        }                                                                    \
-    } while (0)
-
 int wait(gwaoi_strips *s) {
     s->waits++;
-    S_TRY(hipStreamSynchronize(s->st));
+    HIP_TRY(s->last_error, hipStreamSynchronize(s->st));
     return GWAOI_OK;
 }
 
 template <class T>
-int grow(gwaoi_strips *s, T **p, size_t &cap, size_t need) {
-    if (need <= cap && *p) return GWAOI_OK;
-    const size_t c = std::max<size_t>({need + need / 4, cap * 2, 256});
+int grow(gwaoi_strips *s, gw::DevBuf<T> &b, size_t need) {
+    if (need <= b.cap() && b) return GWAOI_OK;
+    const size_t c = std::max<size_t>({need + need / 4, b.cap() * 2, 256});
     if (int rc = wait(s)) return rc;  // nothing queued may still use the old buffer
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc((void **)p, c * sizeof(T));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        s->last_error = std::string("hipMalloc: ") + hipGetErrorString(e);
-        return e == hipErrorOutOfMemory ? GWAOI_ENOMEM : GWAOI_EDEVICE;
-    }
-    cap = c;
-    return GWAOI_OK;
+    return gw::alloc_all(s->last_error, b, c);
 }
 
 int ensure_split(gwaoi_strips *s, uint32_t K, uint32_t nb) {
     const size_t n = (size_t)K * nb + 1;
-    if (int rc = grow(s, &s->counts, s->counts_cap, n)) return rc;
-    if (int rc = grow(s, &s->scan_tmp, s->scan_cap, gw::scan_tmp_elems(n) + 16)) return rc;
+    if (int rc = grow(s, s->counts, n)) return rc;
+    if (int rc = grow(s, s->scan_tmp, gw::scan_tmp_elems(n) + 16)) return rc;
     return GWAOI_OK;
 }
 
 int ensure_fsplit(gwaoi_strips *s, uint32_t G) {
     const size_t n = (size_t)2 * G + 1;
-    if (int rc = grow(s, &s->fcounts, s->fcounts_cap, n)) return rc;
-    if (int rc = grow(s, &s->fscan_tmp, s->fscan_cap, gw::scan_tmp_elems(n) + 16)) return rc;
+    if (int rc = grow(s, s->fcounts, n)) return rc;
+    if (int rc = grow(s, s->fscan_tmp, gw::scan_tmp_elems(n) + 16)) return rc;
     return GWAOI_OK;
 }
 
 int ensure_moves(gwaoi_strips *s, size_t n) {
-    if (n <= s->m_cap && s->m_slot) return GWAOI_OK;
-    size_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    const size_t need = std::max<size_t>(n, s->m_cap * 2);
+    if (n <= s->m_seq.cap() && s->m_seq) return GWAOI_OK;
+    const size_t need = std::max<size_t>(n, s->m_seq.cap() * 2);
     int rc;
-    if ((rc = grow(s, &s->m_slot, c0, need)) || (rc = grow(s, &s->m_x, c1, need)) ||
-        (rc = grow(s, &s->m_z, c2, need)) || (rc = grow(s, &s->m_seq, c3, need))) {
-        s->m_cap = 0;
-        return rc;
+    if ((rc = grow(s, s->m_slot, need)) || (rc = grow(s, s->m_x, need)) || (rc = grow(s, s->m_z, need)) ||
+        (rc = grow(s, s->m_seq, need))) {
+        s->m_slot.reset();
+        s->m_x.reset();
+        s->m_z.reset();
+        s->m_seq.reset();
     }
-    s->m_cap = std::min({c0, c1, c2, c3});
-    return GWAOI_OK;
+    return rc;
 }
 
 int strip_err(gwaoi_strips *s, uint32_t e, const char *where) {
@@ -680,9 +657,9 @@ int launch_filter(gwaoi_strips *s, uint64_t tcap) {
     uint64_t cap = 0;
     gw::world_flush_events(s->w, &wev, &dcnt, &cap);
     const uint64_t need = s->last_kept + s->last_kept / 8 + 2 * tcap + 65536;
-    if (s->out_cap < need)
-        if (int rc = grow(s, &s->out, s->out_cap, need)) return rc;
-    s->pend_ocap = s->out_cap;
+    if (s->out.cap() < need)
+        if (int rc = grow(s, s->out, need)) return rc;
+    s->pend_ocap = s->out.cap();
     const uint32_t G = std::max(1u, std::min<uint32_t>(FILTER_BLOCKS, cdivu(std::max<uint64_t>(cap, 1), BT)));
     if (int rc = ensure_fsplit(s, G)) return rc;
     hipStream_t st = s->st;
@@ -691,11 +668,11 @@ int launch_filter(gwaoi_strips *s, uint64_t tcap) {
                                nullptr, nullptr, nullptr, 0);
     gw::scan_exclusive(s->fcounts, s->fcounts, (size_t)2 * G + 1, s->fscan_tmp, st);
     k_filter<<<G, BT, 0, st>>>(1, ev, dcnt, cap, s->cur, s->prv, s->ptick, s->ttick, s->tick, s->geo, s->fcounts,
-                               s->fcounts, s->tcnt, s->out, s->out_cap);
-    k_tele_place<<<64, 256, 0, st>>>(s->fcounts, G, s->tcnt, s->tpairs, s->tpairs + tcap, s->out, s->out_cap);
+                               s->fcounts, s->tcnt, s->out, s->out.cap());
+    k_tele_place<<<64, 256, 0, st>>>(s->fcounts, G, s->tcnt, s->tpairs, s->tpairs + tcap, s->out, s->out.cap());
     k_tick_totals<<<1, 64, 0, st>>>(s->fcounts, G, s->tcnt, s->terr, s->small_d + SM_TICK);
-    S_TRY(hipGetLastError());
-    S_TRY(hipMemcpyAsync(s->small_h + SM_TICK, s->small_d + SM_TICK, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(s->last_error, hipGetLastError());
+    HIP_TRY(s->last_error, hipMemcpyAsync(s->small_h + SM_TICK, s->small_d + SM_TICK, 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     return GWAOI_OK;
 }
 
@@ -755,14 +732,6 @@ int gwaoi_strips_destroy(gwaoi_strips *s) {
     if (!s) return GWAOI_EINVAL;
     if (s->pending) (void)complete(s, false);
     if (s->st) (void)hipStreamSynchronize(s->st);
-    void *dev[] = {s->cur, s->prv, s->ptick, s->ttick, s->counts, s->scan_tmp, s->err, s->small_d, s->kstat,
-                   s->m_slot, s->m_x, s->m_z, s->m_seq, s->tcnt, s->tpairs, s->out, s->fcounts, s->fscan_tmp,
-                   s->terr};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    if (s->small_h) (void)hipHostFree(s->small_h);
-    if (s->row_h) (void)hipHostFree(s->row_h);
-    if (s->h_events) (void)hipHostFree(s->h_events);
     delete s;
     return GWAOI_OK;
     });
@@ -811,16 +780,8 @@ int gwaoi_strips_create(gwaoi_world *w, uint32_t space, const gwaoi_strips_confi
         gwaoi_strips_destroy(s);
         return rc;
     };
-    if (hipMalloc((void **)&s->cur, N * sizeof(Rec16)) != hipSuccess ||
-        hipMalloc((void **)&s->prv, N * sizeof(Rec16)) != hipSuccess ||
-        hipMalloc((void **)&s->ptick, N * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&s->ttick, N * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&s->err, sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&s->terr, sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&s->small_d, SM_WORDS * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void **)&s->kstat, (GWAOI_MAX_STRIPS + 1) * KS * sizeof(int)) != hipSuccess ||
-        hipMalloc((void **)&s->tcnt, 2 * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc((void **)&s->small_h, SM_WORDS * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess)
+    if (gw::alloc_all(s->last_error, s->cur, N, s->prv, N, s->ptick, N, s->ttick, N, s->err, 1, s->terr, 1, s->small_d,
+                      SM_WORDS, s->kstat, (GWAOI_MAX_STRIPS + 1) * KS, s->tcnt, 2, s->small_h, SM_WORDS))
         return fail(GWAOI_ENOMEM);
     std::memset(s->small_h, 0, SM_WORDS * sizeof(uint32_t));
     if (hipMemsetAsync(s->cur, 0xFF, N * sizeof(Rec16), s->st) != hipSuccess ||  // x = NaN: absent
@@ -856,13 +817,13 @@ int route_launch(gwaoi_strips *s, const gwaoi_halo_rec *d_ops, size_t n) {
     s->routed = false;
     if (int rc = ensure_split(s, K, nb)) return rc;
     hipStream_t st = s->st;
-    S_TRY(hipMemsetAsync(s->err, 0, sizeof(uint32_t), st));
+    HIP_TRY(s->last_error, hipMemsetAsync(s->err, 0, sizeof(uint32_t), st));
     k_kstat_init<<<1, 64, 0, st>>>(s->kstat, s->geo.S);
     k_route<<<nb, BT, 0, st>>>(0, d_ops, (uint32_t)n, s->cur, s->geo, s->counts, nullptr, nb, s->err, nullptr,
                                nullptr, s->kstat);
     gw::scan_exclusive(s->counts, s->counts, (size_t)K * nb + 1, s->scan_tmp, st);
     k_totals<<<1, 128, 0, st>>>(s->counts, K, nb, s->err, s->small_d + SM_ROUTE);
-    S_TRY(hipGetLastError());
+    HIP_TRY(s->last_error, hipGetLastError());
     s->r_ops = d_ops;
     s->r_n = (uint32_t)n;
     s->r_nb = nb;
@@ -874,9 +835,9 @@ int route_launch(gwaoi_strips *s, const gwaoi_halo_rec *d_ops, size_t n) {
 int route_finish(gwaoi_strips *s, uint64_t *counts) {
     const uint32_t K = s->geo.S + 1;
     hipStream_t st = s->st;
-    S_TRY(hipMemcpyAsync(s->small_h + SM_ROUTE, s->small_d + SM_ROUTE, (K + 2) * sizeof(uint32_t),
+    HIP_TRY(s->last_error, hipMemcpyAsync(s->small_h + SM_ROUTE, s->small_d + SM_ROUTE, (K + 2) * sizeof(uint32_t),
                          hipMemcpyDeviceToHost, st));
-    S_TRY(hipMemcpyAsync(s->small_h + SM_KIND, s->kstat, (size_t)s->geo.S * KS * sizeof(int), hipMemcpyDeviceToHost,
+    HIP_TRY(s->last_error, hipMemcpyAsync(s->small_h + SM_KIND, s->kstat, (size_t)s->geo.S * KS * sizeof(int), hipMemcpyDeviceToHost,
                          st));
     if (int rc = wait(s)) return rc;  // the one host wait of a strip tick
     if (int rc = complete_or_break(s, true)) return rc;
@@ -915,7 +876,7 @@ int gwaoi_strips_route_begin(gwaoi_strips *s, const gwaoi_halo_rec *d_ops, size_
     }
     if (int rc = route_launch(s, d_ops, n)) return rc;
     k_route_row<<<1, 256, 0, s->st>>>(s->small_d + SM_ROUTE, s->kstat, s->geo.S, d_row);
-    S_TRY(hipGetLastError());
+    HIP_TRY(s->last_error, hipGetLastError());
     s->row_pending = true;
     return GWAOI_OK;
     });
@@ -926,10 +887,9 @@ int gwaoi_strips_route_end(gwaoi_strips *s, const uint32_t *d_matrix, const uint
     if (!s || !d_matrix || !h_matrix || !counts || !s->row_pending) return GWAOI_EINVAL;
     s->row_pending = false;
     const size_t words = (size_t)s->geo.S * row_words(s->geo.S);
-    if (!s->row_h) {
-        S_TRY(hipHostMalloc((void **)&s->row_h, words * sizeof(uint32_t), hipHostMallocDefault));
-    }
-    S_TRY(hipMemcpyAsync(s->row_h, d_matrix, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s->st));
+    if (!s->row_h)
+        if (int rc = gw::alloc_pinned(s->last_error, s->row_h, words)) return rc;
+    HIP_TRY(s->last_error, hipMemcpyAsync(s->row_h, d_matrix, words * sizeof(uint32_t), hipMemcpyDeviceToHost, s->st));
     if (int rc = route_finish(s, counts)) return rc;
     // every strip's route error (its own was checked by route_finish)
     const uint32_t W = row_words(s->geo.S);
@@ -970,7 +930,7 @@ int gwaoi_strips_route_scatter(gwaoi_strips *s, gwaoi_halo_rec *d_send, gwaoi_te
     s->routed = false;
     k_route<<<s->r_nb, BT, 0, s->st>>>(1, s->r_ops, s->r_n, s->cur, s->geo, s->counts, s->counts, s->r_nb, s->err,
                                        d_send, d_tele, nullptr);
-    S_TRY(hipGetLastError());  // complete in stream order on the world's stream (gwaoi_stream): no host wait
+    HIP_TRY(s->last_error, hipGetLastError());  // complete in stream order on the world's stream (gwaoi_stream): no host wait
     return GWAOI_OK;
     });
 }
@@ -993,7 +953,7 @@ int gwaoi_strips_tick_async(gwaoi_strips *s, const gwaoi_halo_rec *d_local, size
     const uint32_t nb = std::max(1u, cdivu(n_all, BT));
     if (int rc = ensure_split(s, 3, nb)) return rc;
     if (int rc = ensure_moves(s, std::max<size_t>(n_all, 1))) return rc;
-    S_TRY(hipMemsetAsync(s->terr, 0, sizeof(uint32_t), st));
+    HIP_TRY(s->last_error, hipMemsetAsync(s->terr, 0, sizeof(uint32_t), st));
     k_recv<<<nb, BT, 0, st>>>(0, d_local, (uint32_t)n_local, d_recv, (uint32_t)n_all, s->cur, s->prv, s->ptick, tick,
                               s->max_slots, s->counts, nullptr, nb, s->terr, nullptr, nullptr, nullptr, nullptr, nullptr);
     gw::scan_exclusive(s->counts, s->counts, (size_t)3 * nb + 1, s->scan_tmp, st);
@@ -1002,13 +962,13 @@ int gwaoi_strips_tick_async(gwaoi_strips *s, const gwaoi_halo_rec *d_local, size
                               nullptr);
     k_recv_check<<<1, 64, 0, st>>>(s->counts, nb, n_move, n_ent, n_lev, s->terr);
     if (n_tele) k_tele_mark<<<cdivu(n_tele, 256), 256, 0, st>>>(d_tele, (uint32_t)n_tele, s->ttick, tick, s->max_slots);
-    S_TRY(hipGetLastError());
+    HIP_TRY(s->last_error, hipGetLastError());
     // ---- the world's ops, all device batches: Leaves, Enters, Moves (one record per slot)
     auto wfail = [&](int rc, const char *what) {
         s->last_error = std::string(what) + ": " + gwaoi_last_error(s->w);
         return rc;
     };
-    const uint64_t *seqs = reinterpret_cast<const uint64_t *>(s->m_seq);
+    const uint64_t *seqs = reinterpret_cast<const uint64_t *>(s->m_seq.get());
     if (n_lev)
         if (int rc = gwaoi_leave_batch_device(s->w, s->space, s->m_slot + n_move + n_ent, n_lev))
             return wfail(rc, "world leaves");
@@ -1024,21 +984,21 @@ int gwaoi_strips_tick_async(gwaoi_strips *s, const gwaoi_halo_rec *d_local, size
     s->pend_regrows = dbg.event_regrows;
     if (int rc = gwaoi_tick_begin(s->w)) return wfail(rc, "world tick");
     // ---- teleporter pairs: one pass into buffers that hold every possible pair (n (n-1) per kind)
-    S_TRY(hipMemsetAsync(s->tcnt, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(s->last_error, hipMemsetAsync(s->tcnt, 0, 2 * sizeof(unsigned long long), st));
     uint64_t tcap = n_tele > 1 ? (uint64_t)n_tele * (n_tele - 1) : 0;
     if (tcap > TELE_PAIRS_MAX) {  // a teleport storm: count first (one more host wait), then size exactly
         k_tele_pairs<<<cdivu(n_tele, 256), 256, 0, st>>>(0, d_tele, (uint32_t)n_tele, s->geo, s->tcnt, nullptr,
                                                          nullptr, 0);
         unsigned long long hc[2];
-        S_TRY(hipMemcpyAsync(hc, s->tcnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+        HIP_TRY(s->last_error, hipMemcpyAsync(hc, s->tcnt, sizeof(hc), hipMemcpyDeviceToHost, st));
         if (int rc = wait(s)) return rc;
         tcap = std::max<uint64_t>(std::max(hc[0], hc[1]), 1);
-        S_TRY(hipMemsetAsync(s->tcnt, 0, 2 * sizeof(unsigned long long), st));
+        HIP_TRY(s->last_error, hipMemsetAsync(s->tcnt, 0, 2 * sizeof(unsigned long long), st));
     }
     // the pair buffers hold at least 2^16 pairs per kind: a tick-to-tick change of the teleporter
     // count does not reallocate them (a reallocation waits for the stream)
     tcap = std::max<uint64_t>(tcap, 1u << 16);
-    if (int rc = grow(s, &s->tpairs, s->tpairs_cap, 2 * tcap + 1)) return rc;
+    if (int rc = grow(s, s->tpairs, 2 * tcap + 1)) return rc;
     if (n_tele > 1)
         k_tele_pairs<<<cdivu(n_tele, 256), 256, 0, st>>>(1, d_tele, (uint32_t)n_tele, s->geo, s->tcnt, s->tpairs,
                                                          s->tpairs + tcap, tcap);
@@ -1074,14 +1034,14 @@ int gwaoi_strips_tick(gwaoi_strips *s, const gwaoi_halo_rec *d_local, size_t n_l
     if (int rc = ensure_split(s, 3, nb)) return rc;
     hipStream_t st = s->st;
     int *ks = s->kstat + (size_t)GWAOI_MAX_STRIPS * KS;
-    S_TRY(hipMemsetAsync(s->err, 0, sizeof(uint32_t), st));
+    HIP_TRY(s->last_error, hipMemsetAsync(s->err, 0, sizeof(uint32_t), st));
     k_kstat_init<<<1, 64, 0, st>>>(ks, 1);
     k_recv<<<nb, BT, 0, st>>>(0, d_local, (uint32_t)n_local, d_recv, (uint32_t)n_all, s->cur, s->prv, s->ptick,
                               s->tick + 1, s->max_slots, s->counts, nullptr, nb, s->err, nullptr, nullptr, nullptr,
                               nullptr, ks);
-    S_TRY(hipGetLastError());
-    S_TRY(hipMemcpyAsync(s->small_h + SM_RECV, s->err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    S_TRY(hipMemcpyAsync(s->small_h + SM_RECV + 2, ks, KS * sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(s->last_error, hipGetLastError());
+    HIP_TRY(s->last_error, hipMemcpyAsync(s->small_h + SM_RECV, s->err, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(s->last_error, hipMemcpyAsync(s->small_h + SM_RECV + 2, ks, KS * sizeof(int), hipMemcpyDeviceToHost, st));
     if (int rc = wait(s)) return rc;
     if (int rc = strip_err(s, s->small_h[SM_RECV], "recv")) return rc;
     const int *k = reinterpret_cast<const int *>(s->small_h + SM_RECV + 2);
@@ -1105,7 +1065,7 @@ int gwaoi_strips_events_device(gwaoi_strips *s, const uint32_t **d_enter, const 
     return gw::api_guard([&]() -> int {
     if (!s) return GWAOI_EINVAL;
     if (int rc = complete_or_break(s, false)) return rc;
-    if (d_enter) *d_enter = reinterpret_cast<const uint32_t *>(s->out);
+    if (d_enter) *d_enter = reinterpret_cast<const uint32_t *>(s->out.get());
     if (d_leave) *d_leave = reinterpret_cast<const uint32_t *>(s->out + s->n_enter);
     return GWAOI_OK;
     });
@@ -1116,16 +1076,10 @@ int gwaoi_strips_events(gwaoi_strips *s, gwaoi_events *out) {
     if (!s || !out) return GWAOI_EINVAL;
     if (int rc = complete_or_break(s, false)) return rc;
     const uint64_t tot = s->n_enter + s->n_leave;
-    if (tot > s->h_cap || !s->h_events) {
-        if (s->h_events) (void)hipHostFree(s->h_events);
-        s->h_events = nullptr;
-        s->h_cap = 0;
-        const size_t c = std::max<size_t>(tot + tot / 4, 1024);
-        S_TRY(hipHostMalloc((void **)&s->h_events, 2 * c * sizeof(uint32_t), hipHostMallocDefault));
-        s->h_cap = c;
-    }
+    if (2 * tot > s->h_events.cap() || !s->h_events)
+        if (int rc = gw::alloc_pinned(s->last_error, s->h_events, 2 * std::max<size_t>(tot + tot / 4, 1024))) return rc;
     if (tot) {
-        S_TRY(hipMemcpyAsync(s->h_events, s->out, tot * sizeof(uint2), hipMemcpyDeviceToHost, s->st));
+        HIP_TRY(s->last_error, hipMemcpyAsync(s->h_events, s->out, tot * sizeof(uint2), hipMemcpyDeviceToHost, s->st));
         if (int rc = wait(s)) return rc;
     }
     out->n_enter = s->n_enter;

@@ -24,6 +24,7 @@
 
 #include "gwaoi_device.h"
 #include "gwaoi_internal.h"
+#include "gwaoi_mem.h"
 #include "../../include/gwaoi_sync.h"
 
 #include <hip/hip_runtime.h>
@@ -1076,21 +1077,21 @@ __global__ void k_part_offsets(const uint32_t *__restrict__ scanned, uint32_t pa
 
 struct SyncState {
     gwaoi_world *w = nullptr;
-    hipStream_t st = nullptr;
+    hipStream_t st = nullptr;  // view: the world's stream
     uint32_t max_slots = 0;
     // device, per slot
-    uint4 *slots = nullptr;   // SLOT_U4 per slot (the allocation); the fields below point into it
+    DevBuf<uint4> slots;   // SLOT_U4 per slot (the allocation); the four views below point into it
     uint4 *eid = nullptr, *cid = nullptr;
     uint32_t *sst = nullptr;  // gate, space, syncing, flags
     float4 *pos = nullptr;
-    unsigned long long *cl = nullptr;  // 2 per slot: Position / yaw last-writer claims
-    uint32_t *oflag = nullptr, *oflag_n = nullptr;  // decode: slots flagged outside every AOI space
-    uint32_t oflag_cap = 0;                           // entries of oflag (max_slots)
-    bool decoded = false;                           // a decode ran since the last collect
-    uint32_t *h_ndec = nullptr;                     // pinned: oflag_n after the last decode
-    hipEvent_t ndec_ev = nullptr;                   // that copy
+    DevBuf<unsigned long long> cl;  // 2 per slot: Position / yaw last-writer claims
+    DevBuf<uint32_t> oflag, oflag_n;  // decode: slots flagged outside every AOI space
+    uint32_t oflag_cap = 0;           // entries of oflag (max_slots)
+    bool decoded = false;             // a decode ran since the last collect
+    PinnedBuf<uint32_t> h_ndec;       // oflag_n after the last decode
+    Event ndec_ev;                    // that copy
     // id -> slot hash table (device, host mirror)
-    uint4 *htab = nullptr;  // 4 per bucket: 3 keys, (slot, slot, slot, -)
+    DevBuf<uint4> htab;  // 4 per bucket: 3 keys, (slot, slot, slot, -)
     uint32_t hcap = 0, hused = 0;  // entries (3 per 64-B bucket), live + tombstones
     uint32_t hbuckets = 0;         // power of two
     std::vector<uint4> h_hkey;
@@ -1110,78 +1111,41 @@ struct SyncState {
     std::vector<uint32_t> left;  // slots flagged outside the frame since the last collect (host ops)
     unsigned long long claim_next = 1;
     // staging (pinned host + device), reused once the previous upload has landed
-    void *h_stage = nullptr, *d_stage = nullptr;
-    size_t stage_cap = 0;
-    hipEvent_t stage_ev = nullptr;
+    PinnedBuf<char> h_stage;  // the two grow together, d_stage last (its capacity is the pair's)
+    DevBuf<char> d_stage;
+    Event stage_ev;
     bool stage_pending = false;
     // decode arenas: alive until the flush that consumes them
     struct Chunk {
-        char *p;
-        size_t cap, used;
+        DevBuf<char> buf;
+        size_t used;
     };
     std::vector<Chunk> arena;
     uint64_t arena_tick = ~0ull;
     // collect scratch / outputs
-    uint32_t *blk_cnt = nullptr, *scan_tmp = nullptr;
-    size_t blk_cap = 0, scan_cap = 0;
-    unsigned long long *d_off = nullptr;
-    size_t off_cap = 0;
-    uint8_t *h_offp = nullptr;  // pinned: d_off (and the extra word) on the host
-    size_t h_offp_cap = 0;
-    uint32_t *d_left = nullptr;
-    size_t left_cap = 0;
-    // fan-out scratch, frame order (fan_cap entries each)
-    uint32_t *f_snd = nullptr, *f_rg = nullptr, *f_cnt = nullptr, *f_sb = nullptr;
-    uint32_t *scr = nullptr;  // fan-out hits (sender entries), receiver runs
-    size_t scr_cap = 0;
-    unsigned long long *scr_cursor = nullptr;
-    uint4 *f_rec = nullptr;  // 2 per entry
-    uint4 *f_frec = nullptr, *f_cid = nullptr;
-    size_t fan_cap = 0;
-    uint4 *out = nullptr, *out_d = nullptr;
-    size_t out_cap = 0, outd_cap = 0;  // in uint4
+    DevBuf<uint32_t> blk_cnt, scan_tmp;
+    DevBuf<unsigned long long> d_off;
+    PinnedBuf<uint8_t> h_offp;  // d_off (and the extra word) on the host
+    DevBuf<uint32_t> d_left;
+    // fan-out scratch, frame order: the seven grow together (f_rec: 2 per entry)
+    DevBuf<uint32_t> f_snd, f_rg, f_cnt, f_sb;
+    DevBuf<uint4> f_rec, f_frec, f_cid;
+    DevBuf<uint32_t> scr;  // fan-out hits (sender entries), receiver runs
+    DevBuf<unsigned long long> scr_cursor;
+    DevBuf<uint4> out, out_d;
     std::vector<unsigned long long> h_off_raw;
     std::vector<uint64_t> h_off, h_off_c, h_off_d;
-    uint8_t *h_rec = nullptr, *h_rec_d = nullptr;
-    size_t h_rec_cap = 0, h_recd_cap = 0;
+    PinnedBuf<uint8_t> h_rec, h_rec_d;
     // broadcast collect: the host form's uploaded messages, the total / error word, and outputs
     // of its own (valid until the next broadcast collect, whatever the other collects do)
-    uint32_t *cast_in = nullptr;
-    size_t cast_in_cap = 0;
-    unsigned long long *cast_sc = nullptr;
-    uint4 *cast_out = nullptr;
-    size_t cast_out_cap = 0;  // in uint4
-    uint8_t *h_cast = nullptr;
-    size_t h_cast_cap = 0;
+    DevBuf<uint32_t> cast_in;
+    DevBuf<unsigned long long> cast_sc;
+    DevBuf<uint4> cast_out;
+    PinnedBuf<uint8_t> h_cast;
     std::vector<uint64_t> h_off_cast;
 };
 
 namespace {
-
-template <class T>
-int salloc(SyncState *S, T **p, size_t n) {
-    *p = nullptr;
-    if (hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        world_set_error(S->w, "sync: hipMalloc failed");
-        return GWAOI_ENOMEM;
-    }
-    return GWAOI_OK;
-}
-template <class T>
-void sfree(T *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
-
-#define SY_TRY(expr)                                                                     \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            world_set_error(S->w, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-            return GWAOI_EDEVICE;                                                        \
-        }                                                                                \
-    } while (0)
 
 enum Arr { A_CGATE, A_QSPACE, A_SYNCING, A_SFLAGS, A_HVAL, A_N32 };
 enum Arr128 { B_EID, B_CID, B_HKEY, B_N128 };
@@ -1193,7 +1157,7 @@ ArrTable table32(SyncState *S) {
     T.p[A_SYNCING] = S->sst + SST_SYNCING;
     T.p[A_SFLAGS] = S->sst + SST_FLAGS;
     for (int a = A_CGATE; a <= A_SFLAGS; ++a) T.stride[a] = SLOT_W;
-    T.p[A_HVAL] = reinterpret_cast<uint32_t *>(S->htab);  // index: the slot word of an entry (hval_word)
+    T.p[A_HVAL] = reinterpret_cast<uint32_t *>(S->htab.get());  // index: the slot word of an entry (hval_word)
     T.stride[A_HVAL] = 1;
     return T;
 }
@@ -1213,19 +1177,15 @@ void put128(SyncState *S, Arr128 a, uint32_t idx, uint4 v) { S->w128.push_back(W
 
 int ensure_stage(SyncState *S, size_t bytes) {
     if (S->stage_pending) {
-        SY_TRY(hipEventSynchronize(S->stage_ev));
+        HIP_TRY(S->w, hipEventSynchronize(S->stage_ev));
         S->stage_pending = false;
     }
-    if (bytes <= S->stage_cap) return GWAOI_OK;
-    if (S->h_stage) (void)hipHostFree(S->h_stage);
-    sfree(S->d_stage);
-    S->h_stage = nullptr;
-    S->stage_cap = 0;
+    if (bytes <= S->d_stage.cap()) return GWAOI_OK;
     const size_t cap = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-    SY_TRY(hipHostMalloc(&S->h_stage, cap, hipHostMallocDefault));
-    if (int rc = salloc(S, (char **)&S->d_stage, cap)) return rc;
-    S->stage_cap = cap;
-    return GWAOI_OK;
+    S->d_stage.reset();
+    int rc = alloc_pinned(S->w, S->h_stage, cap);
+    if (!rc && (rc = alloc_all(S->w, S->d_stage, cap))) S->h_stage.reset();
+    return rc;
 }
 
 // Keep the last write per (array, index): one scatter launch has no order.
@@ -1252,13 +1212,12 @@ int push(SyncState *S) {
     const size_t total = b128 + b32 + bside;
     if (!total) return GWAOI_OK;
     if (int rc = ensure_stage(S, total)) return rc;
-    char *h = static_cast<char *>(S->h_stage);
-    char *d = static_cast<char *>(S->d_stage);
+    char *h = S->h_stage, *d = S->d_stage;
     std::memcpy(h, S->w128.data(), b128);
     std::memcpy(h + b128, S->w32.data(), b32);
     std::memcpy(h + b128 + b32, S->side.data(), bside);
-    SY_TRY(hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, S->st));
-    SY_TRY(hipEventRecord(S->stage_ev, S->st));
+    HIP_TRY(S->w, hipMemcpyAsync(d, h, total, hipMemcpyHostToDevice, S->st));
+    HIP_TRY(S->w, hipEventRecord(S->stage_ev, S->st));
     S->stage_pending = true;
     // 128-bit writes first (hash keys before the values that publish them)
     if (!S->w128.empty())
@@ -1273,7 +1232,7 @@ int push(SyncState *S) {
         k_side_claim<<<cdivu(n, ST), ST, 0, S->st>>>(o, n, S->cl, S->sst);
         k_side_write<<<cdivu(n, ST), ST, 0, S->st>>>(o, n, S->cl, S->pos);
     }
-    SY_TRY(hipGetLastError());
+    HIP_TRY(S->w, hipGetLastError());
     S->w32.clear();
     S->w128.clear();
     S->side.clear();
@@ -1294,13 +1253,11 @@ int create(gwaoi_world *w, SyncState **out) {
     S->hcap = cap;
     const size_t N = v.max_slots;
     S->oflag_cap = (uint32_t)N;
-    int rc;
-    if ((rc = salloc(S, &S->slots, SLOT_U4 * N)) || (rc = salloc(S, &S->cl, 2 * N)) || (rc = salloc(S, &S->oflag, N)) ||
-        (rc = salloc(S, &S->oflag_n, 1)) || (rc = salloc(S, &S->htab, 4 * (size_t)nbk))) {
+    if (int rc = alloc_all(w, S->slots, SLOT_U4 * N, S->cl, 2 * N, S->oflag, N, S->oflag_n, 1, S->htab, 4 * (size_t)nbk)) {
         sync_destroy(S);
         return rc;
     }
-    S->sst = reinterpret_cast<uint32_t *>(S->slots);
+    S->sst = reinterpret_cast<uint32_t *>(S->slots.get());
     S->pos = reinterpret_cast<float4 *>(S->slots + 1);
     S->eid = S->slots + 2;
     S->cid = S->slots + 3;
@@ -1308,13 +1265,13 @@ int create(gwaoi_world *w, SyncState **out) {
               hipMemsetAsync(S->cl, 0, N * 16, S->st) == hipSuccess &&
               hipMemsetAsync(S->oflag_n, 0, 4, S->st) == hipSuccess &&
               hipMemsetAsync(S->htab, 0xFF, (size_t)nbk * 64, S->st) == hipSuccess &&  // every entry H_EMPTY
-              hipEventCreateWithFlags(&S->stage_ev, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&S->ndec_ev, hipEventDisableTiming) == hipSuccess &&
-              hipHostMalloc((void **)&S->h_ndec, 4, hipHostMallocDefault) == hipSuccess;
+              S->stage_ev.create(hipEventDisableTiming) == GWAOI_OK && S->ndec_ev.create(hipEventDisableTiming) == GWAOI_OK &&
+              S->h_ndec.alloc(1) == GWAOI_OK;
     if (!ok) {
         sync_destroy(S);
         return GWAOI_EDEVICE;
     }
+    *S->h_ndec = 0;  // read after a wait for ndec_ev, which a failed first decode launch never records
     // space of every slot in call order (the world may hold entities already)
     std::vector<uint4> qs(N);
     for (uint32_t s = 0; s < N; ++s) qs[s] = make_uint4(NO_GATE, world_slot_space(w, s), 0u, 0u);
@@ -1400,8 +1357,8 @@ int h_rehash(SyncState *S) {
         S->h_tab[hkey_vec(h)] = S->h_hkey[h];
         reinterpret_cast<uint32_t *>(S->h_tab.data())[hval_word(h)] = S->h_hval[h];
     }
-    SY_TRY(hipMemcpyAsync(S->htab, S->h_tab.data(), S->h_tab.size() * 16, hipMemcpyHostToDevice, S->st));
-    SY_TRY(hipStreamSynchronize(S->st));  // h_tab is pageable staging
+    HIP_TRY(S->w, hipMemcpyAsync(S->htab, S->h_tab.data(), S->h_tab.size() * 16, hipMemcpyHostToDevice, S->st));
+    HIP_TRY(S->w, hipStreamSynchronize(S->st));  // h_tab is pageable staging
     return GWAOI_OK;
 }
 
@@ -1428,36 +1385,20 @@ int bind_one(SyncState *S, uint32_t slot, const uint4 &id) {
     return GWAOI_OK;
 }
 
-int ensure_u32(SyncState *S, uint32_t **p, size_t *cap, size_t n) {
-    if (n <= *cap) return GWAOI_OK;
-    sfree(*p);
-    *cap = 0;
-    const size_t c = std::max<size_t>(n + n / 4, 1024);
-    if (int rc = salloc(S, p, c)) return rc;
-    *cap = c;
-    return GWAOI_OK;
+int ensure_u32(SyncState *S, DevBuf<uint32_t> &b, size_t n) {
+    if (n <= b.cap()) return GWAOI_OK;
+    return alloc_all(S->w, b, std::max<size_t>(n + n / 4, 1024));
 }
 
 // (device) records, grown to n uint4
-int ensure_out(SyncState *S, uint4 **p, size_t *cap, size_t n) {
-    if (n <= *cap) return GWAOI_OK;
-    sfree(*p);
-    *cap = 0;
-    const size_t c = std::max<size_t>(n + n / 8, 3 * 1024);
-    if (int rc = salloc(S, p, c)) return rc;
-    *cap = c;
-    return GWAOI_OK;
+int ensure_out(SyncState *S, DevBuf<uint4> &b, size_t n) {
+    if (n <= b.cap()) return GWAOI_OK;
+    return alloc_all(S->w, b, std::max<size_t>(n + n / 8, 3 * 1024));
 }
 
-int ensure_host(SyncState *S, uint8_t **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return GWAOI_OK;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t c = std::max<size_t>(bytes + bytes / 8, 1 << 16);
-    SY_TRY(hipHostMalloc((void **)p, c, hipHostMallocDefault));
-    *cap = c;
-    return GWAOI_OK;
+int ensure_host(SyncState *S, PinnedBuf<uint8_t> &b, size_t bytes) {
+    if (bytes <= b.cap()) return GWAOI_OK;
+    return alloc_pinned(S->w, b, std::max<size_t>(bytes + bytes / 8, 1 << 16));
 }
 
 // Multisplit bases: blk_cnt [parts][nb] -> exclusive scan (parts*nb + 1
@@ -1465,7 +1406,7 @@ int ensure_host(SyncState *S, uint8_t **p, size_t *cap, size_t bytes) {
 int fetch_bases(SyncState *S, uint32_t parts, bool sync);
 
 unsigned long long unpack_bases(SyncState *S, uint32_t parts) {  // -> the extra word
-    const unsigned long long *h = reinterpret_cast<const unsigned long long *>(S->h_offp);
+    const unsigned long long *h = reinterpret_cast<const unsigned long long *>(S->h_offp.get());
     S->h_off_raw.assign(h, h + parts + 1);
     return h[parts + 1];
 }
@@ -1475,25 +1416,22 @@ unsigned long long unpack_bases(SyncState *S, uint32_t parts) {  // -> the extra
 int part_bases(SyncState *S, uint32_t parts, uint32_t nb, bool sync = true, bool copy = true,
                const unsigned long long *extra = nullptr) {
     const size_t n = (size_t)parts * nb + 1;
-    if (int rc = ensure_u32(S, &S->scan_tmp, &S->scan_cap, scan_tmp_elems(n) + 4)) return rc;
-    if (parts + 2 > S->off_cap) {
-        sfree(S->d_off);
-        if (int rc = salloc(S, &S->d_off, parts + 2)) return rc;
-        S->off_cap = parts + 2;
-    }
+    if (int rc = ensure_u32(S, S->scan_tmp, scan_tmp_elems(n) + 4)) return rc;
+    if (parts + 2 > S->d_off.cap())
+        if (int rc = alloc_all(S->w, S->d_off, parts + 2)) return rc;
     scan_exclusive(S->blk_cnt, S->blk_cnt, n, S->scan_tmp, S->st);
     k_part_offsets<<<cdivu(parts + 1, ST), ST, 0, S->st>>>(S->blk_cnt, parts, nb, S->d_off, extra);
-    SY_TRY(hipGetLastError());
+    HIP_TRY(S->w, hipGetLastError());
     return copy ? fetch_bases(S, parts, sync) : GWAOI_OK;
 }
 
 // the bases part_bases left in d_off (and the extra word), to pinned host memory; unpack_bases
 // turns them into h_off_raw once the stream has reached the copy
 int fetch_bases(SyncState *S, uint32_t parts, bool sync) {
-    if (int rc = ensure_host(S, &S->h_offp, &S->h_offp_cap, (parts + 2) * 8)) return rc;
-    SY_TRY(hipMemcpyAsync(S->h_offp, S->d_off, (parts + 2) * 8, hipMemcpyDeviceToHost, S->st));
+    if (int rc = ensure_host(S, S->h_offp, (parts + 2) * 8)) return rc;
+    HIP_TRY(S->w, hipMemcpyAsync(S->h_offp, S->d_off, (parts + 2) * 8, hipMemcpyDeviceToHost, S->st));
     if (sync) {
-        SY_TRY(hipStreamSynchronize(S->st));
+        HIP_TRY(S->w, hipStreamSynchronize(S->st));
         unpack_bases(S, parts);
     }
     return GWAOI_OK;
@@ -1523,20 +1461,20 @@ int collect_sync(gwaoi_world *w, gwaoi_gate_records *out, bool to_host) {
     S->left.clear();
     uint32_t n_dec = 0;
     if (S->decoded) {  // copied behind the last decode: done by now unless that flush is still running
-        SY_TRY(hipEventSynchronize(S->ndec_ev));
+        HIP_TRY(S->w, hipEventSynchronize(S->ndec_ev));
         n_dec = *S->h_ndec;
         S->decoded = false;
         n_dec = std::min(n_dec, S->oflag_cap);  // k_decode lists a slot at most once (atomicOr claim)
     }
     const size_t n_left = left.size() + n_dec;
     if (n_left) {
-        if (int rc = ensure_u32(S, &S->d_left, &S->left_cap, n_left)) return rc;
+        if (int rc = ensure_u32(S, S->d_left, n_left)) return rc;
         if (!left.empty())
-            SY_TRY(hipMemcpyAsync(S->d_left, left.data(), left.size() * 4, hipMemcpyHostToDevice, S->st));
+            HIP_TRY(S->w, hipMemcpyAsync(S->d_left, left.data(), left.size() * 4, hipMemcpyHostToDevice, S->st));
         if (n_dec) {
-            SY_TRY(hipMemcpyAsync(S->d_left + left.size(), S->oflag, (size_t)n_dec * 4, hipMemcpyDeviceToDevice,
+            HIP_TRY(S->w, hipMemcpyAsync(S->d_left + left.size(), S->oflag, (size_t)n_dec * 4, hipMemcpyDeviceToDevice,
                                   S->st));
-            SY_TRY(hipMemsetAsync(S->oflag_n, 0, 4, S->st));
+            HIP_TRY(S->w, hipMemsetAsync(S->oflag_n, 0, 4, S->st));
         }
     }
     const uint32_t G = (uint32_t)S->gate_ids.size();
@@ -1553,22 +1491,16 @@ int collect_sync(gwaoi_world *w, gwaoi_gate_records *out, bool to_host) {
     A.pos = S->pos;
     A.G = G;
     A.nb = nb;
-    if (int rc = ensure_u32(S, &S->blk_cnt, &S->blk_cap, (size_t)G * nb + 1)) return rc;
+    if (int rc = ensure_u32(S, S->blk_cnt, (size_t)G * nb + 1)) return rc;
     A.blk_cnt = S->blk_cnt;
-    if (n_ent > S->fan_cap) {
-        sfree(S->f_snd); sfree(S->f_rg); sfree(S->f_rec); sfree(S->f_frec); sfree(S->f_cid);
-        sfree(S->f_cnt); sfree(S->f_sb);
-        S->fan_cap = 0;
+    if (n_ent > S->f_snd.cap()) {
         const size_t c = std::max<size_t>(n_ent + n_ent / 8, 1024);
-        int rc;
-        if ((rc = salloc(S, &S->f_snd, c)) || (rc = salloc(S, &S->f_rg, c)) ||
-            (rc = salloc(S, &S->f_rec, 2 * c)) || (rc = salloc(S, &S->f_frec, c)) || (rc = salloc(S, &S->f_cid, c)) || (rc = salloc(S, &S->f_cnt, c)) ||
-            (rc = salloc(S, &S->f_sb, c)))
+        if (int rc = alloc_all(S->w, S->f_snd, c, S->f_rg, c, S->f_rec, 2 * c, S->f_frec, c, S->f_cid, c, S->f_cnt, c,
+                               S->f_sb, c))
             return rc;
-        S->fan_cap = c;
     }
     int rc_scr = GWAOI_OK;
-    if (!S->scr_cursor && (rc_scr = salloc(S, &S->scr_cursor, 1))) return rc_scr;
+    if (!S->scr_cursor && (rc_scr = alloc_all(S->w, S->scr_cursor, 1))) return rc_scr;
     A.fcnt = S->f_cnt;
     A.fsb = S->f_sb;
     A.snd = S->f_snd;
@@ -1583,15 +1515,15 @@ int collect_sync(gwaoi_world *w, gwaoi_gate_records *out, bool to_host) {
     if (G && n_ent) {
         // pass 1: hits into the scratch; a run past the capacity is redone after a regrow
         for (int attempt = 0;; ++attempt) {
-            if (S->scr_cap == 0 && (rc_scr = ensure_u32(S, &S->scr, &S->scr_cap, 32 * (size_t)n_ent))) return rc_scr;
+            if (!S->scr && (rc_scr = ensure_u32(S, S->scr, 32 * (size_t)n_ent))) return rc_scr;
             A.scr = S->scr;
-            A.scr_cap = std::min<unsigned long long>(S->scr_cap, SCR_FULL - 1ull);
+            A.scr_cap = std::min<unsigned long long>(S->scr.cap(), SCR_FULL - 1ull);
             if (attempt) {  // (k_fan_prep zeroed them for the first)
-                SY_TRY(hipMemsetAsync(S->scr_cursor, 0, 8, S->st));
-                SY_TRY(hipMemsetAsync(S->blk_cnt + (size_t)G * nb, 0, 4, S->st));
+                HIP_TRY(S->w, hipMemsetAsync(S->scr_cursor, 0, 8, S->st));
+                HIP_TRY(S->w, hipMemsetAsync(S->blk_cnt + (size_t)G * nb, 0, 4, S->st));
             }
             k_fan_hits_wave<<<nb, ST, (size_t)G * 4, S->st>>>(A);
-            SY_TRY(hipGetLastError());
+            HIP_TRY(S->w, hipGetLastError());
             // the per-gate bases are scanned before the capacity check: one host round trip
             // for both (a rerun rewrites every count the scan read).  The write pass follows on
             // the device with the output as it is (the last collect's size), queued before the
@@ -1599,42 +1531,42 @@ int collect_sync(gwaoi_world *w, gwaoi_gate_records *out, bool to_host) {
             // when either capacity fell short, which the host sees below
             if (int rc = part_bases(S, G, nb, false, false, S->scr_cursor)) return rc;
             A.out = S->out;
-            A.out_recs = S->out_cap / 3;
+            A.out_recs = S->out.cap() / 3;
 #ifdef GWAOI_EXP_FW_ROUNDTRIP  // A/B: the write pass launched after the host's sync (before round 6)
             A.out_recs = 0;
 #endif
             if (A.out_recs) {
                 k_fan_write<<<nb, ST, (3 * (size_t)G + 1) * 4, S->st>>>(A);
-                SY_TRY(hipGetLastError());
+                HIP_TRY(S->w, hipGetLastError());
             }
             if (int rc = fetch_bases(S, G, false)) return rc;
-            SY_TRY(hipStreamSynchronize(S->st));
+            HIP_TRY(S->w, hipStreamSynchronize(S->st));
             const unsigned long long used = unpack_bases(S, G);
             if (used <= A.scr_cap) break;
             if (attempt || used >= SCR_FULL) {
                 world_set_error(w, "sync: fan-out scratch exceeds 2^32 entries");
                 return GWAOI_ENOMEM;
             }
-            if ((rc_scr = ensure_u32(S, &S->scr, &S->scr_cap, (size_t)used))) return rc_scr;
+            if ((rc_scr = ensure_u32(S, S->scr, (size_t)used))) return rc_scr;
         }
         total = S->h_off_raw[G];
     }
     if (total > A.out_recs) {  // (first collect, or more records than the output holds)
-        if (int rc = ensure_out(S, &S->out, &S->out_cap, 3 * total)) return rc;
+        if (int rc = ensure_out(S, S->out, 3 * total)) return rc;
         A.out = S->out;
-        A.out_recs = S->out_cap / 3;
+        A.out_recs = S->out.cap() / 3;
         k_fan_write<<<nb, ST, (3 * (size_t)G + 1) * 4, S->st>>>(A);
-        SY_TRY(hipGetLastError());
+        HIP_TRY(S->w, hipGetLastError());
     }
-    if (int rc = ensure_out(S, &S->out, &S->out_cap, 3)) return rc;  // (an empty collect's pointer)
+    if (int rc = ensure_out(S, S->out, 3)) return rc;  // (an empty collect's pointer)
     S->h_off.assign(S->h_off_raw.begin(), S->h_off_raw.end());
     if (to_host) {
-        if (int rc = ensure_host(S, &S->h_rec, &S->h_rec_cap, std::max<uint64_t>(total, 1) * 48)) return rc;
-        if (total) SY_TRY(hipMemcpyAsync(S->h_rec, S->out, total * 48, hipMemcpyDeviceToHost, S->st));
-        SY_TRY(hipStreamSynchronize(S->st));
+        if (int rc = ensure_host(S, S->h_rec, std::max<uint64_t>(total, 1) * 48)) return rc;
+        if (total) HIP_TRY(S->w, hipMemcpyAsync(S->h_rec, S->out, total * 48, hipMemcpyDeviceToHost, S->st));
+        HIP_TRY(S->w, hipStreamSynchronize(S->st));
         fill_out(S, out, S->h_off, S->h_rec);
     } else {
-        fill_out(S, out, S->h_off, reinterpret_cast<const uint8_t *>(S->out));
+        fill_out(S, out, S->h_off, reinterpret_cast<const uint8_t *>(S->out.get()));
     }
     return GWAOI_OK;
 }
@@ -1668,9 +1600,9 @@ int collect_cast(gwaoi_world *w, const uint32_t *slots, const uint32_t *flags, s
             A.m_slot = slots;
             A.m_flags = flags;
         } else {
-            if (int rc = ensure_u32(S, &S->cast_in, &S->cast_in_cap, 2 * n)) return rc;
-            SY_TRY(hipMemcpyAsync(S->cast_in, slots, n * 4, hipMemcpyHostToDevice, S->st));
-            if (flags) SY_TRY(hipMemcpyAsync(S->cast_in + n, flags, n * 4, hipMemcpyHostToDevice, S->st));
+            if (int rc = ensure_u32(S, S->cast_in, 2 * n)) return rc;
+            HIP_TRY(S->w, hipMemcpyAsync(S->cast_in, slots, n * 4, hipMemcpyHostToDevice, S->st));
+            if (flags) HIP_TRY(S->w, hipMemcpyAsync(S->cast_in + n, flags, n * 4, hipMemcpyHostToDevice, S->st));
             A.m_slot = S->cast_in;
             A.m_flags = flags ? S->cast_in + n : nullptr;
         }
@@ -1681,26 +1613,26 @@ int collect_cast(gwaoi_world *w, const uint32_t *slots, const uint32_t *flags, s
         A.per = std::max<uint32_t>(ST / 64, (cdivu(n, CAST_MAX_BLOCKS) + ST / 64 - 1) / (ST / 64) * (ST / 64));
         A.nb = cdivu(n, A.per);
         A.G = G;
-        if (int rc = ensure_u32(S, &S->blk_cnt, &S->blk_cap, (size_t)G * A.nb + 1)) return rc;
+        if (int rc = ensure_u32(S, S->blk_cnt, (size_t)G * A.nb + 1)) return rc;
         A.blk_cnt = S->blk_cnt;
         if (!S->cast_sc)
-            if (int rc = salloc(S, &S->cast_sc, 1)) return rc;
+            if (int rc = alloc_all(S->w, S->cast_sc, 1)) return rc;
         A.sc = S->cast_sc;
-        SY_TRY(hipMemsetAsync(S->cast_sc, 0, 8, S->st));
+        HIP_TRY(S->w, hipMemsetAsync(S->cast_sc, 0, 8, S->st));
         k_cast_count<<<A.nb, ST, (size_t)G * 4, S->st>>>(A);
-        SY_TRY(hipGetLastError());
+        HIP_TRY(S->w, hipGetLastError());
         // as the fan-out: the bases are scanned and the write pass queued with the output as it
         // is (the last broadcast's size) before the one host wait, which brings the per-gate
         // bases, the 64-bit total and the device form's error bits
         if (int rc = part_bases(S, G, A.nb, false, false, S->cast_sc)) return rc;
         A.out = S->cast_out;
-        A.out_recs = S->cast_out_cap / 2;
+        A.out_recs = S->cast_out.cap() / 2;
         if (A.out_recs) {
             k_cast_write<<<A.nb, ST, (size_t)G * 4, S->st>>>(A);
-            SY_TRY(hipGetLastError());
+            HIP_TRY(S->w, hipGetLastError());
         }
         if (int rc = fetch_bases(S, G, false)) return rc;
-        SY_TRY(hipStreamSynchronize(S->st));
+        HIP_TRY(S->w, hipStreamSynchronize(S->st));
         const unsigned long long sc = unpack_bases(S, G);
         if (sc & CAST_E_FLAGS) status = GWAOI_EINVAL;
         if (sc & CAST_E_SLOT) status = GWAOI_EBADSLOT;
@@ -1710,24 +1642,24 @@ int collect_cast(gwaoi_world *w, const uint32_t *slots, const uint32_t *flags, s
             return GWAOI_ECAPACITY;
         }
         if (total > A.out_recs) {  // (first broadcast, or more records than the output holds)
-            if (int rc = ensure_out(S, &S->cast_out, &S->cast_out_cap, 2 * total)) return rc;
+            if (int rc = ensure_out(S, S->cast_out, 2 * total)) return rc;
             A.out = S->cast_out;
-            A.out_recs = S->cast_out_cap / 2;
+            A.out_recs = S->cast_out.cap() / 2;
             k_cast_write<<<A.nb, ST, (size_t)G * 4, S->st>>>(A);
-            SY_TRY(hipGetLastError());
+            HIP_TRY(S->w, hipGetLastError());
         }
         S->h_off_cast.assign(S->h_off_raw.begin(), S->h_off_raw.end());
     }
-    if (int rc = ensure_out(S, &S->cast_out, &S->cast_out_cap, 2)) return rc;  // (an empty result's pointer)
+    if (int rc = ensure_out(S, S->cast_out, 2)) return rc;  // (an empty result's pointer)
     if (!on_device) {
-        if (int rc = ensure_host(S, &S->h_cast, &S->h_cast_cap, std::max<uint64_t>(total, 1) * GWAOI_CAST_REC)) return rc;
+        if (int rc = ensure_host(S, S->h_cast, std::max<uint64_t>(total, 1) * GWAOI_CAST_REC)) return rc;
         if (total)
-            SY_TRY(hipMemcpyAsync(S->h_cast, S->cast_out, total * GWAOI_CAST_REC, hipMemcpyDeviceToHost, S->st));
-        SY_TRY(hipStreamSynchronize(S->st));
+            HIP_TRY(S->w, hipMemcpyAsync(S->h_cast, S->cast_out, total * GWAOI_CAST_REC, hipMemcpyDeviceToHost, S->st));
+        HIP_TRY(S->w, hipStreamSynchronize(S->st));
         fill_out(S, out, S->h_off_cast, S->h_cast);
     } else {
-        SY_TRY(hipStreamSynchronize(S->st));  // (the caller's arrays are free to go; the records are complete)
-        fill_out(S, out, S->h_off_cast, reinterpret_cast<const uint8_t *>(S->cast_out));
+        HIP_TRY(S->w, hipStreamSynchronize(S->st));  // (the caller's arrays are free to go; the records are complete)
+        fill_out(S, out, S->h_off_cast, reinterpret_cast<const uint8_t *>(S->cast_out.get()));
     }
     if (status != GWAOI_OK) world_set_error(w, "sync: broadcast messages with a bad slot or flag were dropped");
     return status;
@@ -1750,11 +1682,10 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
     }
     if (S->arena_tick != ticks_now) {
         if (S->arena.size() > 1) {  // keep the largest chunk only
-            SY_TRY(hipStreamSynchronize(S->st));
+            HIP_TRY(S->w, hipStreamSynchronize(S->st));
             std::sort(S->arena.begin(), S->arena.end(),
-                      [](const SyncState::Chunk &a, const SyncState::Chunk &b) { return a.cap > b.cap; });
-            for (size_t k = 1; k < S->arena.size(); ++k) (void)hipFree(S->arena[k].p);
-            S->arena.resize(1);
+                      [](const SyncState::Chunk &a, const SyncState::Chunk &b) { return a.buf.cap() > b.buf.cap(); });
+            S->arena.erase(S->arena.begin() + 1, S->arena.end());
         }
         for (auto &c : S->arena) c.used = 0;
         S->arena_tick = ticks_now;
@@ -1763,17 +1694,17 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
     const size_t need = 6 * al(n * 4) + al(4) + (on_device ? 0 : al(n * 32));
     SyncState::Chunk *ch = nullptr;
     for (auto &c : S->arena)
-        if (c.cap - c.used >= need) {
+        if (c.buf.cap() - c.used >= need) {
             ch = &c;
             break;
         }
     if (!ch) {
-        SyncState::Chunk c{nullptr, std::max<size_t>(need, 1 << 20), 0};
-        SY_TRY(hipMalloc((void **)&c.p, c.cap));
-        S->arena.push_back(c);
+        SyncState::Chunk c{};
+        if (alloc_all(S->w, c.buf, std::max<size_t>(need, 1 << 20))) return GWAOI_EDEVICE;
+        S->arena.push_back(std::move(c));
         ch = &S->arena.back();
     }
-    char *base = ch->p + ch->used;
+    char *base = ch->buf + ch->used;
     ch->used += need;
     uint32_t *o_slot = reinterpret_cast<uint32_t *>(base);
     float *o_x = reinterpret_cast<float *>(base + al(n * 4));
@@ -1785,7 +1716,7 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
         pay = reinterpret_cast<const uint4 *>(payload);
     } else {
         char *dp = base + 6 * al(n * 4) + al(4);
-        SY_TRY(hipMemcpyAsync(dp, payload, n * 32, hipMemcpyHostToDevice, S->st));
+        HIP_TRY(S->w, hipMemcpyAsync(dp, payload, n * 32, hipMemcpyHostToDevice, S->st));
         pay = reinterpret_cast<const uint4 *>(dp);
     }
     if (int rc = push(S)) return rc;
@@ -1814,8 +1745,8 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
     k_decode<GWAOI_DEC_PER><<<cdivu(n, ST * GWAOI_DEC_PER), ST, 0, S->st>>>(A);
     k_decode_apply<<<cdivu(n, ST), ST, 0, S->st>>>(A);
     k_decode_dups<<<std::min<uint32_t>(cdivu(n, ST), 64u), ST, 0, S->st>>>(A);
-    SY_TRY(hipGetLastError());
-    SY_TRY(hipEventRecord(S->ndec_ev, S->st));
+    HIP_TRY(S->w, hipGetLastError());
+    HIP_TRY(S->w, hipEventRecord(S->ndec_ev, S->st));
     return world_queue_decoded(w, o_slot, o_x, o_z, o_sp, n);
 }
 
@@ -1834,22 +1765,6 @@ bool sync_slot_plain(const SyncState *S, uint32_t slot) { return slot < S->max_s
 void sync_destroy(SyncState *S) {
     if (!S) return;
     if (S->st) (void)hipStreamSynchronize(S->st);
-    sfree(S->slots);
-    sfree(S->cl); sfree(S->oflag); sfree(S->oflag_n);
-    sfree(S->htab);
-    sfree(S->f_snd); sfree(S->f_rg); sfree(S->f_rec); sfree(S->f_frec); sfree(S->f_cid);
-    sfree(S->blk_cnt); sfree(S->scan_tmp); sfree(S->scr); sfree(S->scr_cursor); sfree(S->f_cnt); sfree(S->f_sb); sfree(S->d_off); sfree(S->d_left); sfree(S->out); sfree(S->out_d);
-    sfree(S->d_stage);
-    sfree(S->cast_in); sfree(S->cast_sc); sfree(S->cast_out);
-    if (S->h_cast) (void)hipHostFree(S->h_cast);
-    for (auto &c : S->arena) (void)hipFree(c.p);
-    if (S->h_stage) (void)hipHostFree(S->h_stage);
-    if (S->h_rec) (void)hipHostFree(S->h_rec);
-    if (S->h_rec_d) (void)hipHostFree(S->h_rec_d);
-    if (S->stage_ev) (void)hipEventDestroy(S->stage_ev);
-    if (S->ndec_ev) (void)hipEventDestroy(S->ndec_ev);
-    if (S->h_ndec) (void)hipHostFree(S->h_ndec);
-    if (S->h_offp) (void)hipHostFree(S->h_offp);
     delete S;
 }
 
@@ -2049,7 +1964,7 @@ int gwaoi_collect_client_events(gwaoi_world *w, gwaoi_gate_records *creates, gwa
     uint64_t nc = 0, nd = 0;
     if (G && n_total) {
         const uint32_t nb = cdivu(n_total, ST);
-        if (int rc = ensure_u32(S, &S->blk_cnt, &S->blk_cap, 2 * (size_t)G * nb + 1)) return rc;
+        if (int rc = ensure_u32(S, S->blk_cnt, 2 * (size_t)G * nb + 1)) return rc;
         RouteArgs A{};
         A.ev = v.events;
         A.n_enter = (uint32_t)v.n_enter;
@@ -2064,30 +1979,30 @@ int gwaoi_collect_client_events(gwaoi_world *w, gwaoi_gate_records *creates, gwa
         A.nb = nb;
         A.blk_cnt = S->blk_cnt;
         const size_t lds = 2 * (size_t)G * 4;
-        SY_TRY(hipMemsetAsync(S->blk_cnt + 2 * (size_t)G * nb, 0, 4, S->st));
+        HIP_TRY(S->w, hipMemsetAsync(S->blk_cnt + 2 * (size_t)G * nb, 0, 4, S->st));
         k_route<0><<<nb, ST, lds, S->st>>>(A);
-        SY_TRY(hipGetLastError());
+        HIP_TRY(S->w, hipGetLastError());
         if (int rc = part_bases(S, 2 * G, nb)) return rc;
         const uint64_t split = S->h_off_raw[G];  // creates occupy [0, split) of one index space
         nc = split;
         nd = S->h_off_raw[2 * G] - split;
-        if (int rc = ensure_out(S, &S->out, &S->out_cap, 3 * std::max<uint64_t>(nc, 1))) return rc;
-        if (int rc = ensure_out(S, &S->out_d, &S->outd_cap, 2 * std::max<uint64_t>(nd, 1))) return rc;
+        if (int rc = ensure_out(S, S->out, 3 * std::max<uint64_t>(nc, 1))) return rc;
+        if (int rc = ensure_out(S, S->out_d, 2 * std::max<uint64_t>(nd, 1))) return rc;
         A.out_c = S->out;
         A.out_d = S->out_d;
         A.split = (uint32_t)split;
         k_route<1><<<nb, ST, lds, S->st>>>(A);
-        SY_TRY(hipGetLastError());
+        HIP_TRY(S->w, hipGetLastError());
         for (uint32_t g = 0; g <= G; ++g) {
             S->h_off_c[g] = S->h_off_raw[g];
             S->h_off_d[g] = S->h_off_raw[G + g] - split;
         }
     }
-    if (int rc = ensure_host(S, &S->h_rec, &S->h_rec_cap, std::max<uint64_t>(nc, 1) * 48)) return rc;
-    if (int rc = ensure_host(S, &S->h_rec_d, &S->h_recd_cap, std::max<uint64_t>(nd, 1) * 32)) return rc;
-    if (nc) SY_TRY(hipMemcpyAsync(S->h_rec, S->out, nc * 48, hipMemcpyDeviceToHost, S->st));
-    if (nd) SY_TRY(hipMemcpyAsync(S->h_rec_d, S->out_d, nd * 32, hipMemcpyDeviceToHost, S->st));
-    SY_TRY(hipStreamSynchronize(S->st));
+    if (int rc = ensure_host(S, S->h_rec, std::max<uint64_t>(nc, 1) * 48)) return rc;
+    if (int rc = ensure_host(S, S->h_rec_d, std::max<uint64_t>(nd, 1) * 32)) return rc;
+    if (nc) HIP_TRY(S->w, hipMemcpyAsync(S->h_rec, S->out, nc * 48, hipMemcpyDeviceToHost, S->st));
+    if (nd) HIP_TRY(S->w, hipMemcpyAsync(S->h_rec_d, S->out_d, nd * 32, hipMemcpyDeviceToHost, S->st));
+    HIP_TRY(S->w, hipStreamSynchronize(S->st));
     fill_out(S, creates, S->h_off_c, S->h_rec);
     fill_out(S, destroys, S->h_off_d, S->h_rec_d);
     return GWAOI_OK;

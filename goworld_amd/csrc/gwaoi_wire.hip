@@ -16,6 +16,7 @@
 // device as changed 32-B buckets {key; value} before the next regroup.
 
 #include "gwaoi_internal.h"
+#include "gwaoi_mem.h"
 #include "../../include/gwaoi_wire.h"
 
 #include <hip/hip_runtime.h>
@@ -134,7 +135,7 @@ struct IdTable {
     std::vector<uint4> key;
     std::vector<uint32_t> val;
     std::vector<uint32_t> dirty;
-    uint4 *d = nullptr;
+    gw::DevBuf<uint4> d;
     uint32_t max_val = 0;  // largest value ever set (the key range of the regroup)
 
     uint32_t find(const uint4 &id) const {
@@ -152,21 +153,17 @@ struct IdTable {
 
 struct gwaoi_wire {
     int device = 0;
-    hipStream_t st = nullptr;
+    gw::Stream st;
     std::string err;
     IdTable games, clients;
     // scratch
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr};
-    uint32_t *hist = nullptr, *scan_tmp = nullptr, *head = nullptr, *gkey = nullptr, *gstart = nullptr;
-    uint32_t *small = nullptr;  // [0] n_keep
-    size_t n_cap = 0, hist_cap = 0, scan_cap = 0;
-    uint4 *d_in = nullptr, *d_out = nullptr;
-    size_t in_cap = 0, out_cap = 0;  // bytes
-    uint8_t *h_in = nullptr, *h_out = nullptr;
-    size_t h_in_cap = 0, h_out_cap = 0;
-    uint4 *d_put = nullptr;
-    uint32_t *d_put_idx = nullptr;
-    size_t put_cap = 0;
+    gw::DevBuf<uint32_t> keys[2], vals[2], head, gkey, gstart;  // grown together (ensure_n)
+    gw::DevBuf<uint32_t> hist, scan_tmp;
+    gw::DevBuf<uint32_t> small;  // [0] n_keep
+    gw::DevBuf<uint8_t> d_in, d_out;  // records (16-B aligned), sized in bytes
+    gw::PinnedBuf<uint8_t> h_in, h_out;
+    gw::DevBuf<uint4> d_put;  // 2 per changed bucket; with d_put_idx (one each)
+    gw::DevBuf<uint32_t> d_put_idx;
     std::vector<uint4> h_put;
     std::vector<uint32_t> h_put_idx;
     // last output
@@ -176,44 +173,14 @@ struct gwaoi_wire {
 
 namespace {
 
-#define W_TRY(expr)                                                                      \
-    do {                                                                                 \
-        hipError_t e_ = (expr);                                                          \
-        if (e_ != hipSuccess) {                                                          \
-            w->err = std::string(#expr) + ": " + hipGetErrorString(e_);                  \
-            return GWAOI_EDEVICE;                                                        \
-        }                                                                                \
-    } while (0)
-
-template <class T>
-int walloc(gwaoi_wire *w, T **p, size_t n) {
-    *p = nullptr;
-    if (hipMalloc((void **)p, std::max<size_t>(n, 1) * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        w->err = "hipMalloc failed";
-        return GWAOI_ENOMEM;
-    }
-    return GWAOI_OK;
-}
-template <class T>
-void wfree(T *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
-void hfree(uint8_t *&p) {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-}
-
 int table_init(gwaoi_wire *w, IdTable &t, uint32_t cap) {
-    wfree(t.d);
     t.cap = cap;
     t.used = t.live = 0;
     t.key.assign(cap, make_uint4(0, 0, 0, 0));
     t.val.assign(cap, H_EMPTY);
     t.dirty.clear();
-    if (int rc = walloc(w, &t.d, 2 * (size_t)cap)) return rc;
-    W_TRY(hipMemsetAsync(t.d, 0xFF, (size_t)cap * 32, w->st));  // every value H_EMPTY
+    if (int rc = gw::alloc_all(w->err, t.d, 2 * (size_t)cap)) return rc;
+    HIP_TRY(w->err, hipMemsetAsync(t.d, 0xFF, (size_t)cap * 32, w->st));  // every value H_EMPTY
     return GWAOI_OK;
 }
 
@@ -246,8 +213,8 @@ int table_grow(gwaoi_wire *w, IdTable &t) {
         buf[2 * (size_t)h] = t.key[h];
         buf[2 * (size_t)h + 1] = make_uint4(t.val[h], 0, 0, 0);
     }
-    W_TRY(hipMemcpyAsync(t.d, buf.data(), buf.size() * 16, hipMemcpyHostToDevice, w->st));
-    W_TRY(hipStreamSynchronize(w->st));  // buf is pageable
+    HIP_TRY(w->err, hipMemcpyAsync(t.d, buf.data(), buf.size() * 16, hipMemcpyHostToDevice, w->st));
+    HIP_TRY(w->err, hipStreamSynchronize(w->st));  // buf is pageable
     t.dirty.clear();
     return GWAOI_OK;
 }
@@ -295,14 +262,9 @@ int table_push(gwaoi_wire *w, IdTable &t) {
     std::sort(t.dirty.begin(), t.dirty.end());
     t.dirty.erase(std::unique(t.dirty.begin(), t.dirty.end()), t.dirty.end());
     const size_t n = t.dirty.size();
-    if (n > w->put_cap) {
-        wfree(w->d_put);
-        wfree(w->d_put_idx);
-        w->put_cap = 0;
+    if (n > w->d_put_idx.cap()) {
         const size_t c = std::max<size_t>(n + n / 2, 1024);
-        if (int rc = walloc(w, &w->d_put, 2 * c)) return rc;
-        if (int rc = walloc(w, &w->d_put_idx, c)) return rc;
-        w->put_cap = c;
+        if (int rc = gw::alloc_all(w->err, w->d_put, 2 * c, w->d_put_idx, c)) return rc;
     }
     w->h_put.resize(2 * n);
     w->h_put_idx.assign(t.dirty.begin(), t.dirty.end());
@@ -310,11 +272,11 @@ int table_push(gwaoi_wire *w, IdTable &t) {
         w->h_put[2 * i] = t.key[t.dirty[i]];
         w->h_put[2 * i + 1] = make_uint4(t.val[t.dirty[i]], 0, 0, 0);
     }
-    W_TRY(hipMemcpyAsync(w->d_put, w->h_put.data(), 2 * n * 16, hipMemcpyHostToDevice, w->st));
-    W_TRY(hipMemcpyAsync(w->d_put_idx, w->h_put_idx.data(), n * 4, hipMemcpyHostToDevice, w->st));
+    HIP_TRY(w->err, hipMemcpyAsync(w->d_put, w->h_put.data(), 2 * n * 16, hipMemcpyHostToDevice, w->st));
+    HIP_TRY(w->err, hipMemcpyAsync(w->d_put_idx, w->h_put_idx.data(), n * 4, hipMemcpyHostToDevice, w->st));
     k_wire_put<<<cdivu(n, WT), WT, 0, w->st>>>(w->d_put, w->d_put_idx, (uint32_t)n, t.d);
-    W_TRY(hipGetLastError());
-    W_TRY(hipStreamSynchronize(w->st));  // the pageable staging vectors are reused
+    HIP_TRY(w->err, hipGetLastError());
+    HIP_TRY(w->err, hipStreamSynchronize(w->st));  // the pageable staging vectors are reused
     t.dirty.clear();
     return GWAOI_OK;
 }
@@ -322,58 +284,27 @@ int table_push(gwaoi_wire *w, IdTable &t) {
 int ensure_n(gwaoi_wire *w, size_t n) {
     const size_t hist = gw::radix_hist_elems((uint32_t)std::max<size_t>(n, 1));
     const size_t scan = std::max(gw::scan_tmp_elems(n + 1), gw::scan_tmp_elems(hist)) + 4;
-    if (n + 1 > w->n_cap) {
-        for (int b = 0; b < 2; ++b) {
-            wfree(w->keys[b]);
-            wfree(w->vals[b]);
-        }
-        wfree(w->head);
-        wfree(w->gkey);
-        wfree(w->gstart);
-        w->n_cap = 0;
+    if (n + 1 > w->head.cap()) {
         const size_t c = std::max<size_t>(n + 1 + n / 4, 4096);
-        for (int b = 0; b < 2; ++b) {
-            if (int rc = walloc(w, &w->keys[b], c)) return rc;
-            if (int rc = walloc(w, &w->vals[b], c)) return rc;
-        }
-        if (int rc = walloc(w, &w->head, c)) return rc;
-        if (int rc = walloc(w, &w->gkey, c)) return rc;
-        if (int rc = walloc(w, &w->gstart, c)) return rc;
-        w->n_cap = c;
+        if (int rc = gw::alloc_all(w->err, w->keys[0], c, w->vals[0], c, w->keys[1], c, w->vals[1], c, w->head, c,
+                                   w->gkey, c, w->gstart, c))
+            return rc;
     }
-    if (hist > w->hist_cap) {
-        wfree(w->hist);
-        w->hist_cap = 0;
-        if (int rc = walloc(w, &w->hist, hist)) return rc;
-        w->hist_cap = hist;
-    }
-    if (scan > w->scan_cap) {
-        wfree(w->scan_tmp);
-        w->scan_cap = 0;
-        if (int rc = walloc(w, &w->scan_tmp, scan)) return rc;
-        w->scan_cap = scan;
-    }
+    if (hist > w->hist.cap())
+        if (int rc = gw::alloc_all(w->err, w->hist, hist)) return rc;
+    if (scan > w->scan_tmp.cap())
+        if (int rc = gw::alloc_all(w->err, w->scan_tmp, scan)) return rc;
     return GWAOI_OK;
 }
 
-int ensure_dev(gwaoi_wire *w, uint4 **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return GWAOI_OK;
-    wfree(*p);
-    *cap = 0;
-    const size_t c = std::max<size_t>(bytes + bytes / 4, 1 << 16);
-    if (int rc = walloc(w, (uint8_t **)p, c)) return rc;
-    *cap = c;
-    return GWAOI_OK;
+int ensure_dev(gwaoi_wire *w, gw::DevBuf<uint8_t> &b, size_t bytes) {
+    if (bytes <= b.cap()) return GWAOI_OK;
+    return gw::alloc_all(w->err, b, std::max<size_t>(bytes + bytes / 4, 1 << 16));
 }
 
-int ensure_pinned(gwaoi_wire *w, uint8_t **p, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return GWAOI_OK;
-    hfree(*p);
-    *cap = 0;
-    const size_t c = std::max<size_t>(bytes + bytes / 4, 1 << 16);
-    W_TRY(hipHostMalloc((void **)p, c, hipHostMallocDefault));
-    *cap = c;
-    return GWAOI_OK;
+int ensure_pinned(gwaoi_wire *w, gw::PinnedBuf<uint8_t> &b, size_t bytes) {
+    if (bytes <= b.cap()) return GWAOI_OK;
+    return gw::alloc_pinned(w->err, b, std::max<size_t>(bytes + bytes / 4, 1 << 16));
 }
 
 // One regroup: records of rec_bytes (32 or 48) keyed at id_word, 32-B output
@@ -383,7 +314,7 @@ int regroup(gwaoi_wire *w, const uint8_t *records, size_t n, bool on_device, uin
     if (!w || !out || (n && !records)) return GWAOI_EINVAL;
     if (n > 0x7FFFFFF0ull) return GWAOI_EINVAL;
     if (on_device && (reinterpret_cast<uintptr_t>(records) & 15u)) return GWAOI_EINVAL;
-    W_TRY(hipSetDevice(w->device));
+    HIP_TRY(w->err, hipSetDevice(w->device));
     *out = gwaoi_wire_groups{};
     out->rec_bytes = REC32;
     uint32_t max_key;
@@ -397,21 +328,21 @@ int regroup(gwaoi_wire *w, const uint8_t *records, size_t n, bool on_device, uin
     const int bits = std::max(1, bitlen(max_key + 1u));
     const uint32_t drop = bits >= 32 ? 0xFFFFFFFFu : (1u << bits) - 1u;  // > every key
     if (int rc = ensure_n(w, n)) return rc;
-    if (int rc = ensure_dev(w, &w->d_out, &w->out_cap, std::max<size_t>(n, 1) * REC32)) return rc;
+    if (int rc = ensure_dev(w, w->d_out, std::max<size_t>(n, 1) * REC32)) return rc;
     const uint4 *d_rec = reinterpret_cast<const uint4 *>(records);
     if (!on_device && n) {
-        if (int rc = ensure_pinned(w, &w->h_in, &w->h_in_cap, n * rec_bytes)) return rc;
-        if (int rc = ensure_dev(w, &w->d_in, &w->in_cap, n * rec_bytes)) return rc;
+        if (int rc = ensure_pinned(w, w->h_in, n * rec_bytes)) return rc;
+        if (int rc = ensure_dev(w, w->d_in, n * rec_bytes)) return rc;
         std::memcpy(w->h_in, records, n * rec_bytes);
-        W_TRY(hipMemcpyAsync(w->d_in, w->h_in, n * rec_bytes, hipMemcpyHostToDevice, w->st));
-        d_rec = w->d_in;
+        HIP_TRY(w->err, hipMemcpyAsync(w->d_in, w->h_in, n * rec_bytes, hipMemcpyHostToDevice, w->st));
+        d_rec = reinterpret_cast<const uint4 *>(w->d_in.get());
     }
     const uint32_t words = rec_bytes / 16;
     uint32_t n_keep = 0, n_groups = 0;
     const uint32_t *sk = w->keys[0], *perm = w->vals[0];
     if (n) {
         k_wire_keys<<<cdivu(n, WT), WT, 0, w->st>>>(d_rec, (uint32_t)n, words, id_word, mode, n_disp,
-                                                     tab ? tab->d : nullptr, tab ? tab->cap - 1 : 0u, drop,
+                                                     tab ? tab->d.get() : nullptr, tab ? tab->cap - 1 : 0u, drop,
                                                      w->keys[0], w->vals[0]);
         gw::SortBuffers sb;
         sb.keys[0] = w->keys[0];
@@ -426,32 +357,32 @@ int regroup(gwaoi_wire *w, const uint8_t *records, size_t n, bool on_device, uin
         k_wire_heads<<<cdivu(n + 1, WT), WT, 0, w->st>>>(sk, (uint32_t)n, drop, w->head, w->small);
         gw::scan_exclusive(w->head, w->head, n + 1, w->scan_tmp, w->st);
         k_wire_groups<<<cdivu(n, WT), WT, 0, w->st>>>(sk, w->head, (uint32_t)n, w->gkey, w->gstart);
-        W_TRY(hipGetLastError());
+        HIP_TRY(w->err, hipGetLastError());
         uint32_t sm[2];
-        W_TRY(hipMemcpyAsync(&sm[0], w->small, 4, hipMemcpyDeviceToHost, w->st));
-        W_TRY(hipMemcpyAsync(&sm[1], w->head + n, 4, hipMemcpyDeviceToHost, w->st));
-        W_TRY(hipStreamSynchronize(w->st));
+        HIP_TRY(w->err, hipMemcpyAsync(&sm[0], w->small, 4, hipMemcpyDeviceToHost, w->st));
+        HIP_TRY(w->err, hipMemcpyAsync(&sm[1], w->head + n, 4, hipMemcpyDeviceToHost, w->st));
+        HIP_TRY(w->err, hipStreamSynchronize(w->st));
         n_keep = sm[0];
         n_groups = sm[1];
         if (n_keep)
             k_wire_gather<<<cdivu(2 * (size_t)n_keep, WT), WT, 0, w->st>>>(d_rec, words, src_word, perm, n_keep,
-                                                                         w->d_out);
-        W_TRY(hipGetLastError());
+                                                                         reinterpret_cast<uint4 *>(w->d_out.get()));
+        HIP_TRY(w->err, hipGetLastError());
     }
     w->o_keys.resize(n_groups);
     w->o_start.resize(n_groups);
     if (n_groups) {
-        W_TRY(hipMemcpyAsync(w->o_keys.data(), w->gkey, n_groups * 4, hipMemcpyDeviceToHost, w->st));
-        W_TRY(hipMemcpyAsync(w->o_start.data(), w->gstart, n_groups * 4, hipMemcpyDeviceToHost, w->st));
+        HIP_TRY(w->err, hipMemcpyAsync(w->o_keys.data(), w->gkey, n_groups * 4, hipMemcpyDeviceToHost, w->st));
+        HIP_TRY(w->err, hipMemcpyAsync(w->o_start.data(), w->gstart, n_groups * 4, hipMemcpyDeviceToHost, w->st));
     }
-    const uint8_t *recs_out = reinterpret_cast<const uint8_t *>(w->d_out);
+    const uint8_t *recs_out = w->d_out;
     if (!on_device) {
-        if (int rc = ensure_pinned(w, &w->h_out, &w->h_out_cap, std::max<size_t>(n_keep, 1) * REC32)) return rc;
+        if (int rc = ensure_pinned(w, w->h_out, std::max<size_t>(n_keep, 1) * REC32)) return rc;
         if (n_keep)
-            W_TRY(hipMemcpyAsync(w->h_out, w->d_out, (size_t)n_keep * REC32, hipMemcpyDeviceToHost, w->st));
+            HIP_TRY(w->err, hipMemcpyAsync(w->h_out, w->d_out, (size_t)n_keep * REC32, hipMemcpyDeviceToHost, w->st));
         recs_out = w->h_out;
     }
-    W_TRY(hipStreamSynchronize(w->st));
+    HIP_TRY(w->err, hipStreamSynchronize(w->st));
     w->o_off.resize((size_t)n_groups + 1);
     for (uint32_t g = 0; g < n_groups; ++g) w->o_off[g] = w->o_start[g];
     w->o_off[n_groups] = n_keep;
@@ -474,12 +405,12 @@ int gwaoi_wire_create(int device, gwaoi_wire **out) {
         if (hipSetDevice(device) != hipSuccess) return GWAOI_EDEVICE;
         gwaoi_wire *w = new gwaoi_wire();
         w->device = device;
-        if (hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking) != hipSuccess) {
+        if (w->st.create(hipStreamNonBlocking)) {
             delete w;
             return GWAOI_EDEVICE;
         }
         int rc;
-        if ((rc = walloc(w, &w->small, 4)) || (rc = table_init(w, w->games, 1024)) ||
+        if ((rc = gw::alloc_all(w->err, w->small, 4)) || (rc = table_init(w, w->games, 1024)) ||
             (rc = table_init(w, w->clients, 1024))) {
             gwaoi_wire_destroy(w);
             return rc;
@@ -493,16 +424,6 @@ void gwaoi_wire_destroy(gwaoi_wire *w) {
     if (!w) return;
     (void)hipSetDevice(w->device);
     if (w->st) (void)hipStreamSynchronize(w->st);
-    for (int b = 0; b < 2; ++b) {
-        wfree(w->keys[b]);
-        wfree(w->vals[b]);
-    }
-    wfree(w->hist); wfree(w->scan_tmp); wfree(w->head); wfree(w->gkey); wfree(w->gstart); wfree(w->small);
-    wfree(w->d_in); wfree(w->d_out); wfree(w->d_put); wfree(w->d_put_idx);
-    wfree(w->games.d); wfree(w->clients.d);
-    hfree(w->h_in);
-    hfree(w->h_out);
-    if (w->st) (void)hipStreamDestroy(w->st);
     delete w;
 }
 
@@ -511,7 +432,7 @@ const char *gwaoi_wire_last_error(gwaoi_wire *w) { return w ? w->err.c_str() : "
 int gwaoi_wire_set_entity_games(gwaoi_wire *w, const uint8_t *entity_ids, const uint16_t *game_ids, size_t n) {
     return gw::api_guard([&]() -> int {
         if (!w || (n && !game_ids)) return GWAOI_EINVAL;
-        W_TRY(hipSetDevice(w->device));
+        HIP_TRY(w->err, hipSetDevice(w->device));
         std::vector<uint32_t> v(game_ids, game_ids + n);
         return table_set(w, w->games, entity_ids, v.data(), n, false);
     });
@@ -520,7 +441,7 @@ int gwaoi_wire_set_entity_games(gwaoi_wire *w, const uint8_t *entity_ids, const 
 int gwaoi_wire_remove_entities(gwaoi_wire *w, const uint8_t *entity_ids, size_t n) {
     return gw::api_guard([&]() -> int {
         if (!w) return GWAOI_EINVAL;
-        W_TRY(hipSetDevice(w->device));
+        HIP_TRY(w->err, hipSetDevice(w->device));
         return table_set(w, w->games, entity_ids, nullptr, n, true);
     });
 }
@@ -528,7 +449,7 @@ int gwaoi_wire_remove_entities(gwaoi_wire *w, const uint8_t *entity_ids, size_t 
 int gwaoi_wire_set_clients(gwaoi_wire *w, const uint8_t *client_ids, const uint32_t *client_index, size_t n) {
     return gw::api_guard([&]() -> int {
         if (!w) return GWAOI_EINVAL;
-        W_TRY(hipSetDevice(w->device));
+        HIP_TRY(w->err, hipSetDevice(w->device));
         return table_set(w, w->clients, client_ids, client_index, n, false);
     });
 }
@@ -536,7 +457,7 @@ int gwaoi_wire_set_clients(gwaoi_wire *w, const uint8_t *client_ids, const uint3
 int gwaoi_wire_remove_clients(gwaoi_wire *w, const uint8_t *client_ids, size_t n) {
     return gw::api_guard([&]() -> int {
         if (!w) return GWAOI_EINVAL;
-        W_TRY(hipSetDevice(w->device));
+        HIP_TRY(w->err, hipSetDevice(w->device));
         return table_set(w, w->clients, client_ids, nullptr, n, true);
     });
 }

@@ -10,6 +10,7 @@
 // grid or the event buffer must grow.
 
 #include "gwaoi_internal.h"
+#include "gwaoi_mem.h"
 #include "../../include/gwaoi.h"
 
 #include <hip/hip_runtime.h>
@@ -44,12 +45,11 @@ const char *kStageNames[ST_N] = {"apply",    "keygen",  "sort",   "gather", "cel
                                  "combined", "special", "finish", "d2h"};
 
 struct DevFrame {
-    gw::Rec16 *rec = nullptr;
-    gw::SlotSp *ss = nullptr;
-    uint32_t *key = nullptr;  // cell key of every entry (the next flush's "previous cell")
-    uint32_t *cell_start = nullptr;
-    size_t cell_cap = 0;  // entries allocated in cell_start
-    SpaceGrid *grid = nullptr;
+    gw::DevBuf<gw::Rec16> rec;
+    gw::DevBuf<gw::SlotSp> ss;
+    gw::DevBuf<uint32_t> key;  // cell key of every entry (the next flush's "previous cell")
+    gw::DevBuf<uint32_t> cell_start;
+    gw::DevBuf<SpaceGrid> grid;
     std::vector<SpaceGrid> hgrid;  // host mirror of `grid` (upload only on change)
     uint32_t n = 0;
     uint32_t total_cells = 0;
@@ -74,6 +74,7 @@ struct Run {  // a stretch of the op queue: host ops [hbegin, hend) or a device 
     uint8_t kind;    // device batch: RUN_MOVE, or a structural batch (gwaoi_enter/leave_batch_device)
     uint32_t space;  // RUN_ENTER / RUN_LEAVE: the space
     size_t hbegin, hend;
+    // views (a device batch): the caller's device arrays, or words of a staging half
     const uint32_t *ds;
     const float *dx, *dz;
     const unsigned long long *dseq;  // explicit device seqs (nullptr: seq0 + i)
@@ -178,30 +179,29 @@ struct EvCaps {
 // sets, alternated per launch, so that flush t+1 can be launched before flush
 // t's summary has reached the host (gwaoi_tick_finish with GWAOI_END_NEXT).
 struct FlushSet {
-    gw::Rec16 *srec = nullptr;  // S': previous frame + this flush's ops, previous order
-    gw::SlotSp *sss = nullptr;
-    gw::Rec16 *orec = nullptr;  // previous state in the new frame's order (NaN if absent)
-    uint4 *cand = nullptr;      // combined-pass candidate records of the new frame (x, z, old x, old z; NaN = jumper)
-    gw::TickScalars *sc = nullptr;
-    uint32_t *events = nullptr;  // ev_cap (a,b) pairs: [enters | leaves] in tile order
+    gw::DevBuf<gw::Rec16> srec;  // S': previous frame + this flush's ops, previous order
+    gw::DevBuf<gw::SlotSp> sss;
+    gw::DevBuf<gw::Rec16> orec;  // previous state in the new frame's order (NaN if absent)
+    gw::DevBuf<uint4> cand;      // combined-pass candidate records of the new frame (x, z, old x, old z; NaN = jumper)
+    gw::DevBuf<gw::TickScalars> sc;
+    gw::DevBuf<uint32_t> events;  // ev_cap (a,b) pairs: [enters | leaves] in tile order
     uint64_t ev_cap = 0;         // capacity in directed pairs
     // the pair passes' scratch (evtmp_cap pairs: per-tile chunks of the eight event streams) and the
     // per-tile event totals / stream positions: per set, so that a flush's pair passes and finish
     // can run while the next flush's first kernels (which zero the totals and write the special
     // pass's events) already run on the early stream
-    uint32_t *evtmp = nullptr;
+    gw::DevBuf<uint32_t> evtmp;
     uint64_t evtmp_cap = 0;
-    uint32_t *tile_total = nullptr;
-    unsigned long long *tile_base = nullptr;
+    gw::DevBuf<uint32_t> tile_total;
+    gw::DevBuf<unsigned long long> tile_base;
     size_t tile_entries_cap = 0;
-    hipEvent_t mid_ev = nullptr;  // recorded after the flush's early kernels (the next flush's early stream waits)
-    void *bbox_parts = nullptr;  // bbox level-1 partials
-    uint32_t n_parts = 0;        // ... written by the flush (k_gather's blocks or k_merge_gather's tiles)
-    char *dev_out = nullptr;     // device counts (2 words) | int4 bbox[max_spaces] from kDevBBox on (the bbox fold)
-    char *h_out = nullptr;       // pinned: the flush summary (TickOut + bbox)
-    char *d_hout = nullptr;      // h_out as the device sees it: k_finish writes the summary there
-    hipEvent_t done_ev = nullptr;  // recorded after the flush's last kernel
-    hipEvent_t ev[ST_N][2] = {};   // stage timing
+    gw::Event mid_ev;  // recorded after the flush's early kernels (the next flush's early stream waits)
+    gw::DevBuf<char> bbox_parts;  // bbox level-1 partials
+    uint32_t n_parts = 0;         // ... written by the flush (k_gather's blocks or k_merge_gather's tiles)
+    gw::DevBuf<char> dev_out;     // device counts (2 words) | int4 bbox[max_spaces] from kDevBBox on (the bbox fold)
+    gw::PinnedBuf<char> h_out;    // mapped: the flush summary (TickOut + bbox); k_finish writes it through dev()
+    gw::Event done_ev;  // recorded after the flush's last kernel
+    gw::Event ev[ST_N][2];  // stage timing
     bool ev_used[ST_N] = {};
 };
 
@@ -210,7 +210,7 @@ struct FlushSet {
 struct gwaoi_world {
     gwaoi_config cfg{};
     int device = 0;
-    hipStream_t stream = nullptr;
+    gw::Stream stream;
     uint32_t max_slots = 0, max_spaces = 0;
     float cells_per_dist = 1.0f;  // cells per AOI distance of the grids in use
     // Cell size by density (gwaoi_config.cells_per_dist == 0): clustered crowds want D/3,
@@ -231,34 +231,35 @@ struct gwaoi_world {
     int last_set = 0;    // set of the last committed flush (its events)
 
     // working set (max_slots entries each)
-    uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr};
-    uint32_t *hist = nullptr;
-    uint32_t *scan_tmp = nullptr;
-    size_t scan_tmp_cap = 0;
-    gw::SlotTab sinfo{};  // per slot: last op claim, S' index, space (three arrays)
+    gw::DevBuf<uint32_t> keys[2], vals[2];
+    gw::DevBuf<uint32_t> hist;
+    gw::DevBuf<uint32_t> scan_tmp;
+    // per slot: last op claim, S' index, space (three arrays), and sinfo, the view of them the kernels take
+    gw::DevBuf<unsigned long long> si_lastop;
+    gw::DevBuf<uint32_t> si_rank, si_sp;
+    gw::SlotTab sinfo{};
     // incremental frame sort (grid unchanged): per-cell counts, arrival lists
-    unsigned long long *cnt64 = nullptr, *scan64_tmp = nullptr;
-    uint32_t *arr_pos = nullptr, *arr_idx = nullptr;
-    uint32_t *coll = nullptr;  // slots moved twice in one flush (single-pass apply)
-    uint32_t *special = nullptr;  // per previous-frame tile: keygen saw a special entity (the special pass's skip list)
-    uint32_t *tile_work = nullptr;   // per combined tile: its measured time, then its candidates (k_combined)
-    uint32_t *tile_order = nullptr;  // the next flush's combined tile order, heaviest first (k_tile_order)
-    uint8_t *ework = nullptr;        // per frame entry: log2 of the candidates its lane swept (the next flush's deal)
-    uint32_t *mv_hist = nullptr;  // bucketed apply: the bucket-major histogram, scanned (gw::launch_moves_bucketed)
-    uint4 *mv_binned = nullptr;  // bucketed apply: the ops regrouped by slot bucket (16 B each)
+    gw::DevBuf<unsigned long long> cnt64, scan64_tmp;
+    gw::DevBuf<uint32_t> arr_pos, arr_idx;
+    gw::DevBuf<uint32_t> coll;  // slots moved twice in one flush (single-pass apply)
+    gw::DevBuf<uint32_t> special;  // per previous-frame tile: keygen saw a special entity (the special pass's skip list)
+    gw::DevBuf<uint32_t> tile_work;   // per combined tile: its measured time, then its candidates (k_combined)
+    gw::DevBuf<uint32_t> tile_order;  // the next flush's combined tile order, heaviest first (k_tile_order)
+    gw::DevBuf<uint8_t> ework;        // per frame entry: log2 of the candidates its lane swept (the next flush's deal)
+    gw::DevBuf<uint32_t> mv_hist;  // bucketed apply: the bucket-major histogram, scanned (gw::launch_moves_bucketed)
+    gw::DevBuf<uint4> mv_binned;  // bucketed apply: the ops regrouped by slot bucket (16 B each)
     bool moves_bucketed = false;   // the bucketed apply (max_slots > MV_MIN_SLOTS; GWAOI_MOVES_BUCKETED forces it)
-    size_t cnt64_cap = 0;
     // test and diagnostics flags (GWAOI_F_TEST_*, include/gwaoi.h)
     bool force_radix = false;  // always the full radix sort (checks the incremental sort against it)
     bool force_copy = false;   // S' always copied by the prologue (checks virtual S' against it)
     bool inject_regrow_fail = false;  // the event regrow fails (the poison path)
-    hipEvent_t done_ev = nullptr;  // wait_stream's marker (polled)
-    hipEvent_t order_ev = nullptr;  // gwaoi_stream_after / _before
+    gw::Event done_ev;  // wait_stream's marker (polled)
+    gw::Event order_ev;  // gwaoi_stream_after / _before
     // Overlapped flushes (speculative launches only): flush t+1's early kernels (apply .. gather)
     // run on early_st while flush t's pair passes and finish still run on the stream.  gen counts
     // the enqueues on the stream from anything but a flush; an early stream may skip only work
     // the previous flush queued (gen unchanged since its launch: gen_launch).
-    hipStream_t early_st = nullptr;
+    gw::Stream early_st;
     uint64_t gen = 0, gen_launch = ~0ull;
     bool ovl_ok = false;   // set around a speculative launch (end_begin)
 #ifdef GWAOI_EXP_HOSTTIME  // diagnostics build only: host time per phase of gwaoi_tick_finish(NEXT), printed at destroy
@@ -269,25 +270,22 @@ struct gwaoi_world {
     bool check_stages = false;   // wait after every flush stage (fault diagnosis)
     const char *fault_stage = nullptr;  // stage at the first failed wait
     bool fault_before = false;          // ... the wait before it (else after it)
-    uint32_t *new_slots_d = nullptr;
-    uint32_t *op_slot = nullptr, *op_sp = nullptr;
-    float *op_x = nullptr, *op_z = nullptr;
-    unsigned long long *op_seq = nullptr;
-    size_t op_cap = 0;
-    float *blk = nullptr;        // keygen per-block partials
-    uint32_t *nb_out = nullptr, *nb_count = nullptr;
-    size_t nb_cap = 0;
+    gw::DevBuf<uint32_t> new_slots_d;
+    gw::DevBuf<uint32_t> op_slot, op_sp;  // the five op arrays grow together (ensure_ops)
+    gw::DevBuf<float> op_x, op_z;
+    gw::DevBuf<unsigned long long> op_seq;
+    gw::DevBuf<float> blk;        // keygen per-block partials
+    gw::DevBuf<uint32_t> nb_out, nb_count;
     // per-slot rows of the last flush's events (gwaoi_events_csr), built on request
-    uint32_t *csr_cnt = nullptr, *csr_off = nullptr, *csr_items = nullptr, *csr_long = nullptr;
-    uint64_t csr_items_cap = 0;
-    uint32_t *h_csr_off = nullptr, *h_csr_items = nullptr;
-    uint64_t h_csr_items_cap = 0;
+    gw::DevBuf<uint32_t> csr_cnt, csr_off, csr_items, csr_long;
+    uint64_t csr_items_cap = 0;  // items; csr_items holds twice as many words (items | merge scratch)
+    gw::PinnedBuf<uint32_t> h_csr_off, h_csr_items;
     uint64_t csr_tick = ~0ull;  // flush the device CSR belongs to
 
     // pinned host mirrors
-    uint32_t *h_events = nullptr;
-    uint64_t h_ev_cap = 0;
-    SpaceGrid *h_grid = nullptr;
+    gw::PinnedBuf<uint32_t> h_events;  // mapped: k_pairs_out writes it through dev()
+    uint64_t h_ev_cap = 0;             // in pairs (h_events holds 2 * h_ev_cap words)
+    gw::PinnedBuf<SpaceGrid> h_grid;
 
     // host bookkeeping
     std::vector<uint8_t> alive, in_frame, appended;
@@ -309,36 +307,37 @@ struct gwaoi_world {
     // host move batches (gwaoi_moved_batch) staged as [slots | x | z | space] in pinned memory and sent
     // with one async H2D each (copy stream); they then run as device batches.  Two halves: the calls
     // queued while a flush is in flight stage into the half that flush does not read.
-    uint32_t *h_stage[2] = {nullptr, nullptr}, *d_stage[2] = {nullptr, nullptr};
+    gw::PinnedBuf<uint32_t> h_stage[2];
+    gw::DevBuf<uint32_t> d_stage[2];
     size_t stage_cap[2] = {0, 0}, stage_used[2] = {0, 0};
     int stage_cur = 0;
     // sparse flush (gwaoi_sparse.hip): per-op counts and offsets, and the host ops' upload buffer
     // (sp_ops_layout: pinned -> device in one copy); off with GWAOI_F_NO_SPARSE
-    uint32_t *sp_cnt = nullptr;
-    uint8_t *h_sp_ops = nullptr, *d_sp_ops = nullptr;
+    gw::DevBuf<uint32_t> sp_cnt;
+    gw::PinnedBuf<uint8_t> h_sp_ops;
+    gw::DevBuf<uint8_t> d_sp_ops;
     // the fused form (one launch; GWAOI_F_TEST_SPARSE_SEQUENCE: the kernel sequence): per-op scratch
     // rows of sp_scr_cap events per kind (GWAOI_F_TEST_SPARSE_SCR2: 2), and its arrival counter
-    uint32_t *sp_scr = nullptr, *sp_done = nullptr;
+    gw::DevBuf<uint32_t> sp_scr, sp_done;
     uint32_t sp_scr_cap = 512;
     bool sparse_fused = true;
     bool sparse_on = true;
     // zero-copy batch (gwaoi_moved_batch_stage / _commit): the caller fills [slots | x | z | space]
     size_t resv_n = 0;        // moves reserved (0: no reservation)
-    uint32_t *resv_h = nullptr, *resv_d = nullptr;
+    uint32_t *resv_h = nullptr, *resv_d = nullptr;  // views into h_stage / d_stage[resv_half]
     int resv_half = 0;
     // event copies to the host beside the next flush (gwaoi_tick_finish, GWAOI_END_HOST / _PAIRS)
-    hipStream_t out_st = nullptr;
-    hipEvent_t out_ev = nullptr;
+    gw::Stream out_st;
+    gw::Event out_ev;
     bool out_pending = false;  // a copy-out of events queued by gwaoi_tick_finish, not yet waited for
     bool out_pairs = false;    // ... of one event per mirrored pair (GWAOI_END_PAIRS)
     // the counts of the flush whose events h_events holds (a later commit without a copy-out, e.g.
     // gwaoi_tick_finish without a host mode, changes last_n_* but not the host copy)
     uint64_t out_n_enter = 0, out_n_leave = 0;
-    uint32_t *d_h_events = nullptr;  // h_events as the device sees it (k_pairs_out writes through it)
     // GWAOI_F_UNIQUE_MOVES: the Moved batches of one flush never repeat a slot (no claims, no fixup)
     bool unique_moves = false;
-    hipStream_t copy_st = nullptr;  // staging H2D copies
-    hipEvent_t copy_ev = nullptr;   // recorded after the last staging copy
+    gw::Stream copy_st;  // staging H2D copies
+    gw::Event copy_ev;   // recorded after the last staging copy
     bool copy_pending = false;      // the flush must wait for copy_ev
     StagePool pool;
     unsigned stage_threads = 8;  // host threads validating + staging one big batch
@@ -398,34 +397,6 @@ namespace {
         }                                          \
     } while (0)
 
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            w->last_error = std::string(#expr) + ": " + hipGetErrorString(e_);               \
-            return GWAOI_EDEVICE;                                                             \
-        }                                                                                     \
-    } while (0)
-
-template <class T>
-int dalloc(gwaoi_world *w, T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    hipError_t e = hipMalloc((void **)p, n * sizeof(T));
-    if (e != hipSuccess) {
-        w->last_error = std::string("hipMalloc: ") + hipGetErrorString(e);
-        *p = nullptr;
-        return e == hipErrorOutOfMemory ? GWAOI_ENOMEM : GWAOI_EDEVICE;
-    }
-    return GWAOI_OK;
-}
-
-template <class T>
-void dfree(T *&p) {
-    if (p) (void)hipFree((void *)p);
-    p = nullptr;
-}
-
 inline bool finite2(float x, float z) { return std::isfinite(x) && std::isfinite(z); }
 
 void stage_begin(gwaoi_world *w, FlushSet &S, Stage s) {
@@ -461,26 +432,22 @@ void stage_collect(gwaoi_world *w, FlushSet &S) {
 // wake-up latency to every tick.
 int wait_stream(gwaoi_world *w) {
     if (!w->done_ev) {
-        HIP_TRY(hipStreamSynchronize(w->stream));
+        HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
         return GWAOI_OK;
     }
-    HIP_TRY(hipEventRecord(w->done_ev, w->stream));
+    HIP_TRY(w->last_error, hipEventRecord(w->done_ev, w->stream));
     hipError_t e;
     while ((e = hipEventQuery(w->done_ev)) == hipErrorNotReady) __builtin_ia32_pause();
-    HIP_TRY(e);
+    HIP_TRY(w->last_error, e);
     return GWAOI_OK;
 }
 
 int ensure_scan_tmp(gwaoi_world *w, size_t n) {
     size_t need = gw::scan_tmp_elems(n) + 16;
-    if (need <= w->scan_tmp_cap) return GWAOI_OK;
+    if (need <= w->scan_tmp.cap()) return GWAOI_OK;
     w->gen++;  // (an enqueue on the stream that no flush made: the next flush's early kernels wait for it)
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    dfree(w->scan_tmp);
-    int rc = dalloc(w, &w->scan_tmp, need);
-    if (rc) return rc;
-    w->scan_tmp_cap = need;
-    return GWAOI_OK;
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
+    return gw::alloc_all(w->last_error, w->scan_tmp, need);
 }
 
 // Room for `pairs` directed events in set S's event buffer and for a scratch extent of `extent`
@@ -492,20 +459,18 @@ int ensure_scan_tmp(gwaoi_world *w, size_t n) {
 int ensure_events(gwaoi_world *w, FlushSet &S, uint64_t pairs, uint64_t extent, bool exact = false) {
     if (pairs <= S.ev_cap && extent <= S.evtmp_cap) return GWAOI_OK;
     w->gen++;
-    HIP_TRY(hipStreamSynchronize(w->stream));
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
     int rc;
     if (pairs > S.ev_cap) {
         const uint64_t cap = exact ? pairs : std::max<uint64_t>(pairs + pairs / 4, S.ev_cap * 2);
-        dfree(S.events);
         S.ev_cap = 0;
-        if ((rc = dalloc(w, &S.events, 2 * cap))) return rc;
+        if ((rc = gw::alloc_all(w->last_error, S.events, 2 * cap))) return rc;
         S.ev_cap = cap;
     }
     if (extent > S.evtmp_cap) {
         const uint64_t cap = std::max<uint64_t>(extent + extent / 4, S.evtmp_cap * 2);
-        dfree(S.evtmp);
         S.evtmp_cap = 0;
-        if ((rc = dalloc(w, &S.evtmp, 2 * cap))) return rc;
+        if ((rc = gw::alloc_all(w->last_error, S.evtmp, 2 * cap))) return rc;
         S.evtmp_cap = cap;
     }
     return GWAOI_OK;
@@ -516,15 +481,9 @@ int ensure_tile_entries(gwaoi_world *w, FlushSet &S, size_t entries) {
     if (entries + 1 <= S.tile_entries_cap) return GWAOI_OK;
     w->gen++;
     size_t cap = std::max<size_t>(entries + 1 + entries / 4, 1024);
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    dfree(S.tile_total);
-    dfree(S.tile_base);
-    int rc;
-    if ((rc = dalloc(w, &S.tile_total, gw::tile_total_elems(cap))) ||
-        (rc = dalloc(w, &S.tile_base, cap))) {
-        S.tile_entries_cap = 0;
-        return rc;
-    }
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
+    S.tile_entries_cap = 0;
+    if (int rc = gw::alloc_all(w->last_error, S.tile_total, gw::tile_total_elems(cap), S.tile_base, cap)) return rc;
     S.tile_entries_cap = cap;
     return GWAOI_OK;
 }
@@ -541,71 +500,49 @@ int ensure_host_events(gwaoi_world *w, uint64_t pairs) {
     if (int rc = finish_out(w)) return rc;
     if (pairs <= w->h_ev_cap) return GWAOI_OK;
     uint64_t cap = std::max<uint64_t>(pairs + pairs / 4, 1024);
-    if (w->h_events) (void)hipHostFree(w->h_events);
-    w->h_events = w->d_h_events = nullptr;
     w->h_ev_cap = 0;
     // mapped and coherent: k_pairs_out writes it from the device, through its device address
-    HIP_TRY(hipHostMalloc((void **)&w->h_events, 2 * cap * sizeof(uint32_t), hipHostMallocMapped | hipHostMallocCoherent));
-    HIP_TRY(hipHostGetDevicePointer((void **)&w->d_h_events, w->h_events, 0));
+    if (int rc = gw::alloc_pinned(w->last_error, w->h_events, 2 * cap, w->h_events.kMapped)) return rc;
     w->h_ev_cap = cap;
     return GWAOI_OK;
 }
 
 int ensure_ops(gwaoi_world *w, size_t n) {
-    if (n <= w->op_cap) return GWAOI_OK;
+    if (n <= w->op_slot.cap()) return GWAOI_OK;
     w->gen++;  // (an enqueue on the stream that no flush made: the next flush's early kernels wait for it)
-    size_t cap = std::max<size_t>(n, w->op_cap * 2);
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    dfree(w->op_slot);
-    dfree(w->op_sp);
-    dfree(w->op_x);
-    dfree(w->op_z);
-    dfree(w->op_seq);
-    int rc;
-    if ((rc = dalloc(w, &w->op_slot, cap)) || (rc = dalloc(w, &w->op_sp, cap)) || (rc = dalloc(w, &w->op_x, cap)) ||
-        (rc = dalloc(w, &w->op_z, cap)) || (rc = dalloc(w, &w->op_seq, cap))) {
-        w->op_cap = 0;
-        return rc;
-    }
-    w->op_cap = cap;
-    return GWAOI_OK;
+    size_t cap = std::max<size_t>(n, w->op_slot.cap() * 2);
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
+    return gw::alloc_all(w->last_error, w->op_slot, cap, w->op_sp, cap, w->op_x, cap, w->op_z, cap, w->op_seq, cap);
 }
 
 int ensure_incr(gwaoi_world *w, size_t cells) {
     const size_t need = cells + 1;
-    if (need <= w->cnt64_cap) return GWAOI_OK;
+    if (need <= w->cnt64.cap()) return GWAOI_OK;
     w->gen++;  // (an enqueue on the stream that no flush made: the next flush's early kernels wait for it)
     const size_t cap = std::max(need + need / 4, (size_t)1024);
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    dfree(w->cnt64);
-    dfree(w->scan64_tmp);
-    dfree(w->arr_pos);
-    w->cnt64_cap = 0;
-    int rc;
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
     // arr_pos: the arrival cursors, the per-cell stayer shifts, the changed cells (incremental_sort)
-    if ((rc = dalloc(w, &w->cnt64, cap)) || (rc = dalloc(w, &w->arr_pos, 3 * cap)) ||
-        (rc = dalloc(w, &w->scan64_tmp, gw::incr_sort_tmp_elems(cap))))
+    if (int rc = gw::alloc_all(w->last_error, w->cnt64, cap, w->arr_pos, 3 * cap, w->scan64_tmp,
+                               gw::incr_sort_tmp_elems(cap)))
         return rc;
-    HIP_TRY(hipMemsetAsync(w->scan64_tmp, 0, gw::incr_sort_tmp_elems(cap) * sizeof(unsigned long long), w->stream));
-    HIP_TRY(hipMemsetAsync(w->cnt64, 0, cap * sizeof(unsigned long long), w->stream));  // then kept zero by the sort
-    w->cnt64_cap = cap;
+    hipError_t e = hipMemsetAsync(w->scan64_tmp, 0, gw::incr_sort_tmp_elems(cap) * sizeof(unsigned long long), w->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(w->cnt64, 0, cap * sizeof(unsigned long long), w->stream);  // then kept zero by the sort
+    if (e != hipSuccess) {  // not zeroed: the group stays empty, and the next call grows it again
+        w->cnt64.reset();
+        w->arr_pos.reset();
+        w->scan64_tmp.reset();
+    }
+    HIP_TRY(w->last_error, e);
     return GWAOI_OK;
 }
 
 int ensure_cells(gwaoi_world *w, DevFrame &f, size_t cells) {
     size_t need = cells + 1;
-    if (need <= f.cell_cap) return GWAOI_OK;
+    if (need <= f.cell_start.cap()) return GWAOI_OK;
     w->gen++;  // (an enqueue on the stream that no flush made: the next flush's early kernels wait for it)
     size_t cap = std::max(need + need / 4, (size_t)1024);
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    dfree(f.cell_start);
-    int rc = dalloc(w, &f.cell_start, cap);
-    if (rc) {
-        f.cell_cap = 0;
-        return rc;
-    }
-    f.cell_cap = cap;
-    return GWAOI_OK;
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
+    return gw::alloc_all(w->last_error, f.cell_start, cap);
 }
 
 void push_host_op(gwaoi_world *w, uint32_t slot, float x, float z, uint32_t sp, uint64_t seq) {
@@ -688,6 +625,35 @@ void defer(gwaoi_world *w, Deferred::Kind k, uint32_t slot, uint32_t space, floa
     q.z = z;
     q.seq = seq;
     w->deferred.push_back(q);
+}
+
+Run device_run(const uint32_t *ds, const float *dx, const float *dz, size_t n) {
+    Run r{};
+    r.device = true;
+    r.ds = ds;
+    r.dx = dx;
+    r.dz = dz;
+    r.dn = n;
+    return r;
+}
+
+// The one way a device run joins the queue.  Its ops take the seqs from seq_next on, unless it
+// carries explicit ones (a Leave's seq is never compared: like gwaoi_leave, it takes none).  While
+// a flush is in flight the run is deferred, then queued for the next flush at the commit.
+void queue_run(gwaoi_world *w, Run r) {
+    if (!r.dseq) {
+        r.seq0 = w->seq_next;
+        if (r.kind != RUN_LEAVE) w->seq_next += r.dn;
+    }
+    if (w->in_flight) {
+        Deferred q{};
+        q.kind = Deferred::RUN;
+        q.run = r;
+        w->deferred.push_back(q);
+        return;
+    }
+    w->runs.push_back(r);
+    w->n_ops += r.dn;
 }
 
 float o2f(int i) {
@@ -810,7 +776,7 @@ int bitlen(uint32_t v) {
     return b;
 }
 
-gw::TickOut *tick_out(FlushSet &S) { return reinterpret_cast<gw::TickOut *>(S.h_out); }
+gw::TickOut *tick_out(FlushSet &S) { return reinterpret_cast<gw::TickOut *>(S.h_out.get()); }
 const int4 *tick_bbox(FlushSet &S) { return reinterpret_cast<const int4 *>(S.h_out + sizeof(gw::TickOut)); }
 // The device boxes a line apart from the device counts: k_finish's copy block storing a count while
 // its fold block's atomics land on the boxes shared one line and stalled both (6 us at config 3).
@@ -857,11 +823,11 @@ EvCaps launch_pair_passes(gwaoi_world *w, FlushSet &S, DevFrame &Fn, DevFrame &P
     // tile order + TickOut + the per-space bboxes for the next flush's grid (one launch)
     stage_begin(w, S, ST_FINISH);
     gw::launch_finish(S.tile_total, S.tile_base, entries, half, S.evtmp, S.events,
-                      caps.tmp, caps.out, S.sc, reinterpret_cast<gw::TickOut *>(S.d_hout), Fn.n,
+                      caps.tmp, caps.out, S.sc, reinterpret_cast<gw::TickOut *>(S.h_out.dev()), Fn.n,
                       dev_bbox(S), w->n_space_ids, S.bbox_parts, S.n_parts,
-                      reinterpret_cast<int4 *>(S.d_hout + sizeof(gw::TickOut)),
+                      reinterpret_cast<int4 *>(S.h_out.dev() + sizeof(gw::TickOut)),
                       order ? w->tile_work : nullptr, order ? w->tile_order : nullptr,
-                      reinterpret_cast<uint32_t *>(S.dev_out), st);
+                      reinterpret_cast<uint32_t *>(S.dev_out.get()), st);
     stage_end(w, S, ST_FINISH);
     return caps;
 }
@@ -902,7 +868,7 @@ int tick_launch(gwaoi_world *w) {
     (void)hipGetLastError();  // the launch check below must see this flush's launches only
     // a copy-out still reading a flush set's events (gwaoi_tick_finish) ends before this
     // flush writes into a set
-    if (w->out_pending) HIP_TRY(hipStreamWaitEvent(st, w->out_ev, 0));
+    if (w->out_pending) HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->out_ev, 0));
     // grid for this flush
     uint32_t total_cells = 0, total_rows = 0;
     choose_grids(w, total_cells, total_rows);
@@ -944,16 +910,16 @@ int tick_launch(gwaoi_world *w) {
 #endif
     if (ovl) {
         st = w->early_st;
-        HIP_TRY(hipStreamWaitEvent(st, w->fs[set ^ 1].mid_ev, 0));
+        HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->fs[set ^ 1].mid_ev, 0));
         w->dbg.overlapped_flushes++;
     }
     if (!grid_same) {
-        HIP_TRY(hipMemcpyAsync(Fn.grid, w->h_grid, sizeof(SpaceGrid) * ns, hipMemcpyHostToDevice, st));
-        Fn.hgrid.assign(w->h_grid, w->h_grid + ns);
+        HIP_TRY(w->last_error, hipMemcpyAsync(Fn.grid, w->h_grid, sizeof(SpaceGrid) * ns, hipMemcpyHostToDevice, st));
+        Fn.hgrid.assign(w->h_grid.get(), w->h_grid + ns);
     }
     // the staged move batches' H2D copies (copy stream) land before the flush reads them
     if (w->copy_pending) {
-        HIP_TRY(hipStreamWaitEvent(st, w->copy_ev, 0));
+        HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->copy_ev, 0));
         w->copy_pending = false;
     }
     // device runs only (device Enter/Leave batches included: their ops carry the space, the appended
@@ -998,7 +964,7 @@ int tick_launch(gwaoi_world *w) {
         tz.n_spaces = w->n_space_ids;
         tz.n_unique = n_unique;
     } else if (incr)
-        gw::launch_prologue(S.sc, reinterpret_cast<uint32_t *>(w->cnt64),
+        gw::launch_prologue(S.sc, reinterpret_cast<uint32_t *>(w->cnt64.get()),
                             gw::scan_rezeroes_counts() ? 0 : 2 * ((size_t)total_cells + 1), S.tile_total,
                             gw::tile_total_elems(entries), dev_bbox(S), w->n_space_ids, n_copy, P.rec, P.ss, S.srec, S.sss, mark,
                             w->max_slots, w->sinfo, tick_id, n_unique, st);
@@ -1010,7 +976,7 @@ int tick_launch(gwaoi_world *w) {
     // ---- apply queued ops onto S'
     stage_begin(w, S, ST_APPLY);
     if (n_app_host) {
-        HIP_TRY(hipMemcpyAsync(w->new_slots_d, w->new_slots.data(), n_app_host * sizeof(uint32_t),
+        HIP_TRY(w->last_error, hipMemcpyAsync(w->new_slots_d, w->new_slots.data(), n_app_host * sizeof(uint32_t),
                                hipMemcpyHostToDevice, st));
         gw::launch_init_appended(w->new_slots_d, n_app_host, n_prev, S.srec, S.sss, w->sinfo, w->max_slots, S.sc, st);
     }
@@ -1038,11 +1004,11 @@ int tick_launch(gwaoi_world *w) {
         for (const Run &r : w->runs) {
             if (r.device) continue;
             const size_t k = r.hend - r.hbegin;
-            HIP_TRY(hipMemcpyAsync(w->op_slot + hat, w->h_op_slot.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w->op_x + hat, w->h_op_x.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w->op_z + hat, w->h_op_z.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w->op_sp + hat, w->h_op_sp.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(w->op_seq + hat, w->h_op_seq.data() + r.hbegin, k * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_slot + hat, w->h_op_slot.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_x + hat, w->h_op_x.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_z + hat, w->h_op_z.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_sp + hat, w->h_op_sp.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_seq + hat, w->h_op_seq.data() + r.hbegin, k * 8, hipMemcpyHostToDevice, st));
             hat += k;
         }
         for (int pass = 0; pass < 2; ++pass) {
@@ -1095,7 +1061,7 @@ int tick_launch(gwaoi_world *w) {
         spj.O_ss = s_ss_view;
         spj.seq_base = seq_base;
         spj.sc = S.sc;
-        spj.tmp = reinterpret_cast<uint2 *>(S.evtmp);
+        spj.tmp = reinterpret_cast<uint2 *>(S.evtmp.get());
         spj.cap = S.evtmp_cap;
         spj.tile_total = S.tile_total;
         spj.tile_base = S.tile_base;
@@ -1223,7 +1189,7 @@ int tick_launch(gwaoi_world *w) {
 int wait_done(gwaoi_world *w, hipEvent_t ev) {
     hipError_t e;
     while ((e = hipEventQuery(ev)) == hipErrorNotReady) __builtin_ia32_pause();
-    HIP_TRY(e);
+    HIP_TRY(w->last_error, e);
     return GWAOI_OK;
 }
 
@@ -1308,8 +1274,8 @@ int finish_flight(gwaoi_world *w, const Flight &f, bool host_done, bool *committ
         (void)hipGetLastError();  // a failure of an unrelated earlier call is not this re-run's
         w->gen++;
         gw::launch_zero(S.tile_total, gw::tile_total_elems(f.entries), st);
-        gw::launch_zero(&S.sc->shard[0][0], gw::EV_SHARDS * 32, st);  // event streams
-        gw::launch_zero(S.sc->dbg, gw::DBG_N, st);
+        gw::launch_zero(&S.sc.get()->shard[0][0], gw::EV_SHARDS * 32, st);  // event streams
+        gw::launch_zero(S.sc.get()->dbg, gw::DBG_N, st);
         cap_used = launch_pair_passes(w, S, Fn, P, f.seq_base, f.s_ss_view, true);
         if (cap_used.tmp < need || cap_used.out < r.total64) {
             w->last_error = "pair passes re-run: event buffers did not grow";
@@ -1426,25 +1392,19 @@ int sparse_try(gwaoi_world *w) {
         w->dbg.sparse_declined++;
         return 1;
     };
-    if (!w->sp_cnt && dalloc(w, &w->sp_cnt, gw::sparse_cnt_elems((uint32_t)kSparseMaxOps)) != GWAOI_OK) return give_up();
-    if (!run.device && !w->h_sp_ops) {  // the host ops' one pinned upload buffer
-        if (hipHostMalloc((void **)&w->h_sp_ops, kSpOpsBytes, hipHostMallocDefault) != hipSuccess) {
-            w->h_sp_ops = nullptr;
-            return give_up();
-        }
-        if (dalloc(w, &w->d_sp_ops, kSpOpsBytes) != GWAOI_OK) return give_up();
-    }
+    if (!w->sp_cnt && gw::alloc_all(w->last_error, w->sp_cnt, gw::sparse_cnt_elems((uint32_t)kSparseMaxOps))) return give_up();
+    // the host ops' one pinned upload buffer and its device twin
+    if (!run.device && !w->h_sp_ops && gw::alloc_all(w->last_error, w->h_sp_ops, kSpOpsBytes, w->d_sp_ops, kSpOpsBytes))
+        return give_up();
     const bool fused = w->sparse_fused && k <= gw::sparse_fused_max();
     if (fused && !w->sp_scr) {
-        if (dalloc(w, &w->sp_scr, (size_t)gw::sparse_fused_max() * 2 * w->sp_scr_cap) != GWAOI_OK ||
-            dalloc(w, &w->sp_done, 1) != GWAOI_OK) {
-            dfree(w->sp_scr);
+        if (gw::alloc_all(w->last_error, w->sp_scr, (size_t)gw::sparse_fused_max() * 2 * w->sp_scr_cap, w->sp_done, 1)) {
             w->sparse_fused = false;  // the kernel sequence needs neither
         } else {
-            HIP_TRY(hipMemsetAsync(w->sp_done, 0, sizeof(uint32_t), st));
+            HIP_TRY(w->last_error, hipMemsetAsync(w->sp_done, 0, sizeof(uint32_t), st));
         }
     }
-    if (w->out_pending) HIP_TRY(hipStreamWaitEvent(st, w->out_ev, 0));  // a copy-out still reads S's events
+    if (w->out_pending) HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->out_ev, 0));  // a copy-out still reads S's events
     const uint32_t *d_slot = run.ds;
     const float *d_x = run.dx, *d_z = run.dz;
     const unsigned long long *d_seq = nullptr;
@@ -1453,17 +1413,17 @@ int sparse_try(gwaoi_world *w) {
         std::memcpy(w->h_sp_ops + kSpSlot, w->h_op_slot.data(), k * 4);
         std::memcpy(w->h_sp_ops + kSpX, w->h_op_x.data(), k * 4);
         std::memcpy(w->h_sp_ops + kSpZ, w->h_op_z.data(), k * 4);
-        HIP_TRY(hipMemcpyAsync(w->d_sp_ops, w->h_sp_ops, kSpZ + k * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(w->last_error, hipMemcpyAsync(w->d_sp_ops, w->h_sp_ops, kSpZ + k * 4, hipMemcpyHostToDevice, st));
         d_slot = reinterpret_cast<const uint32_t *>(w->d_sp_ops + kSpSlot);
         d_x = reinterpret_cast<const float *>(w->d_sp_ops + kSpX);
         d_z = reinterpret_cast<const float *>(w->d_sp_ops + kSpZ);
         d_seq = reinterpret_cast<const unsigned long long *>(w->d_sp_ops + kSpSeq);
     } else if (w->copy_pending) {  // the staged batch's H2D lands first
-        HIP_TRY(hipStreamWaitEvent(st, w->copy_ev, 0));
+        HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->copy_ev, 0));
         w->copy_pending = false;
     }
     const uint32_t tick_id = ++w->tick_id;
-    gw::TickOut *res = reinterpret_cast<gw::TickOut *>(S.d_hout);
+    gw::TickOut *res = reinterpret_cast<gw::TickOut *>(S.h_out.dev());
     auto run_sparse = [&](bool fused) -> int {
         if (fused) {
             gw::launch_sparse_fused(P.rec, P.ss, P.key, P.cell_start, P.grid, w->sinfo, d_slot, d_x, d_z, d_seq,
@@ -1575,48 +1535,6 @@ int gwaoi_world_destroy(gwaoi_world *w) {
     if (w->out_st) (void)hipStreamSynchronize(w->out_st);
     if (w->sync) gw::sync_destroy(w->sync);
     w->sync = nullptr;
-    for (DevFrame &f : w->fr) {
-        dfree(f.rec); dfree(f.ss); dfree(f.key); dfree(f.cell_start); dfree(f.grid);
-    }
-    for (FlushSet &S : w->fs) {
-        dfree(S.srec); dfree(S.sss); dfree(S.orec); dfree(S.cand); dfree(S.sc); dfree(S.events);
-        dfree(S.bbox_parts); dfree(S.dev_out); dfree(S.evtmp); dfree(S.tile_total); dfree(S.tile_base);
-        if (S.mid_ev) (void)hipEventDestroy(S.mid_ev);
-        if (S.h_out) (void)hipHostFree(S.h_out);
-        S.h_out = nullptr;
-        for (int st = 0; st < ST_N; ++st)
-            for (int q = 0; q < 2; ++q)
-                if (S.ev[st][q]) (void)hipEventDestroy(S.ev[st][q]);
-        if (S.done_ev) (void)hipEventDestroy(S.done_ev);
-    }
-    for (int i = 0; i < 2; ++i) { dfree(w->keys[i]); dfree(w->vals[i]); }
-    dfree(w->hist); dfree(w->scan_tmp); dfree(w->sinfo.lastop); dfree(w->sinfo.rank); dfree(w->sinfo.sp); dfree(w->new_slots_d);
-    dfree(w->cnt64); dfree(w->scan64_tmp); dfree(w->arr_pos); dfree(w->arr_idx); dfree(w->coll); dfree(w->special);
-    dfree(w->tile_work); dfree(w->tile_order); dfree(w->ework);
-    dfree(w->mv_hist); dfree(w->mv_binned);
-    dfree(w->op_slot); dfree(w->op_sp); dfree(w->op_x); dfree(w->op_z); dfree(w->op_seq);
-    dfree(w->sp_cnt); dfree(w->d_sp_ops); dfree(w->sp_scr); dfree(w->sp_done);
-    if (w->h_sp_ops) (void)hipHostFree(w->h_sp_ops);
-    dfree(w->blk);
-    dfree(w->nb_out); dfree(w->nb_count);
-    dfree(w->csr_cnt); dfree(w->csr_off); dfree(w->csr_items); dfree(w->csr_long);
-    if (w->h_csr_off) (void)hipHostFree(w->h_csr_off);
-    if (w->h_csr_items) (void)hipHostFree(w->h_csr_items);
-    if (w->h_events) (void)hipHostFree(w->h_events);
-    if (w->h_grid) (void)hipHostFree(w->h_grid);
-    for (int h = 0; h < 2; ++h) {
-        if (w->h_stage[h]) (void)hipHostFree(w->h_stage[h]);
-        dfree(w->d_stage[h]);
-    }
-    if (w->copy_ev) (void)hipEventDestroy(w->copy_ev);
-    if (w->copy_st) (void)hipStreamDestroy(w->copy_st);
-    if (w->out_st) (void)hipStreamSynchronize(w->out_st);
-    if (w->out_ev) (void)hipEventDestroy(w->out_ev);
-    if (w->out_st) (void)hipStreamDestroy(w->out_st);
-    if (w->done_ev) (void)hipEventDestroy(w->done_ev);
-    if (w->order_ev) (void)hipEventDestroy(w->order_ev);
-    if (w->stream) (void)hipStreamDestroy(w->stream);
-    if (w->early_st) (void)hipStreamDestroy(w->early_st);
     delete w;
     return GWAOI_OK;
     });
@@ -1660,43 +1578,20 @@ int gwaoi_world_create(const gwaoi_config *cfg, gwaoi_world **out) {
         delete w;
         return GWAOI_EDEVICE;
     }
-    if (hipStreamCreateWithFlags(&w->early_st, hipStreamNonBlocking) != hipSuccess) {
-        w->early_st = nullptr;
+    if (w->early_st.create(hipStreamNonBlocking) || w->stream.create(hipStreamNonBlocking) ||
+        w->copy_st.create(hipStreamNonBlocking) || w->copy_ev.create(hipEventDisableTiming) ||
+        w->out_st.create(hipStreamNonBlocking) || w->out_ev.create(hipEventDisableTiming))
         return fail(GWAOI_EDEVICE);
-    }
-    if (hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking) != hipSuccess) {
-        w->stream = nullptr;
-        return fail(GWAOI_EDEVICE);
-    }
-    if (hipStreamCreateWithFlags(&w->copy_st, hipStreamNonBlocking) != hipSuccess) {
-        w->copy_st = nullptr;
-        return fail(GWAOI_EDEVICE);
-    }
-    if (hipEventCreateWithFlags(&w->copy_ev, hipEventDisableTiming) != hipSuccess) {
-        w->copy_ev = nullptr;
-        return fail(GWAOI_EDEVICE);
-    }
-    if (hipStreamCreateWithFlags(&w->out_st, hipStreamNonBlocking) != hipSuccess) {
-        w->out_st = nullptr;
-        return fail(GWAOI_EDEVICE);
-    }
-    if (hipEventCreateWithFlags(&w->out_ev, hipEventDisableTiming) != hipSuccess) {
-        w->out_ev = nullptr;
-        return fail(GWAOI_EDEVICE);
-    }
     const size_t N = w->max_slots;
+    std::string &err = w->last_error;
     for (DevFrame &f : w->fr) {
-        if ((rc = dalloc(w, &f.rec, N)) || (rc = dalloc(w, &f.ss, N)) || (rc = dalloc(w, &f.key, N)) ||
-            (rc = dalloc(w, &f.grid, w->max_spaces)))
-            return fail(rc);
+        if ((rc = gw::alloc_all(err, f.rec, N, f.ss, N, f.key, N, f.grid, w->max_spaces))) return fail(rc);
         if ((rc = ensure_cells(w, f, 1))) return fail(rc);
     }
     const size_t out_bytes = sizeof(gw::TickOut) + sizeof(int4) * (size_t)w->max_spaces;
     for (FlushSet &S : w->fs) {
-        if ((rc = dalloc(w, &S.srec, N)) || (rc = dalloc(w, &S.sss, N)) || (rc = dalloc(w, &S.orec, N)) ||
-            (rc = dalloc(w, &S.cand, N)) || (rc = dalloc(w, &S.sc, 1)) ||
-            (rc = dalloc(w, (char **)&S.bbox_parts, gw::bbox_part_bytes((uint32_t)N))) ||
-            (rc = dalloc(w, &S.dev_out, kDevBBox + sizeof(int4) * (size_t)w->max_spaces)))
+        if ((rc = gw::alloc_all(err, S.srec, N, S.sss, N, S.orec, N, S.cand, N, S.sc, 1, S.bbox_parts,
+                                gw::bbox_part_bytes((uint32_t)N), S.dev_out, kDevBBox + sizeof(int4) * (size_t)w->max_spaces)))
             return fail(rc);
         // S' records seq 0 (virtual S': never "written")
         if (hipMemset(S.srec, 0, N * sizeof(gw::Rec16)) != hipSuccess) return fail(GWAOI_EDEVICE);
@@ -1705,26 +1600,20 @@ int gwaoi_world_create(const gwaoi_config *cfg, gwaoi_world **out) {
         // k_finish writes the summary here while the host polls done_ev: coherent (uncached, system
         // scope) memory, so that the writes are visible once the event is seen whatever the runtime's
         // default coherence of pinned allocations
-        if (hipHostMalloc((void **)&S.h_out, out_bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&S.d_hout, S.h_out, 0) != hipSuccess)
-            return fail(GWAOI_ENOMEM);
+        if (S.h_out.alloc(out_bytes, S.h_out.kMapped)) return fail(GWAOI_ENOMEM);
         std::memset(S.h_out, 0, out_bytes);
         for (int st = 0; st < ST_N; ++st)
             for (int q = 0; q < 2; ++q)
-                if (hipEventCreate(&S.ev[st][q]) != hipSuccess) return fail(GWAOI_EDEVICE);
-        if (hipEventCreateWithFlags(&S.done_ev, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&S.mid_ev, hipEventDisableTiming) != hipSuccess)
-            return fail(GWAOI_EDEVICE);
+                if (S.ev[st][q].create(hipEventDefault)) return fail(GWAOI_EDEVICE);
+        if (S.done_ev.create(hipEventDisableTiming) || S.mid_ev.create(hipEventDisableTiming)) return fail(GWAOI_EDEVICE);
     }
-    if ((rc = dalloc(w, &w->keys[0], N)) || (rc = dalloc(w, &w->keys[1], N)) || (rc = dalloc(w, &w->vals[0], N)) ||
-        (rc = dalloc(w, &w->vals[1], N)) || (rc = dalloc(w, &w->hist, gw::radix_hist_elems((uint32_t)N))) ||
-        (rc = dalloc(w, &w->sinfo.lastop, N)) || (rc = dalloc(w, &w->sinfo.rank, N)) ||
-        (rc = dalloc(w, &w->sinfo.sp, N)) || (rc = dalloc(w, &w->new_slots_d, N)) || (rc = dalloc(w, &w->arr_idx, N)) ||
-        (rc = dalloc(w, &w->coll, N)) || (rc = dalloc(w, &w->blk, 3 * (N / 256 + 2))) ||
-        (rc = dalloc(w, &w->special, N / 256 + 2)) || (rc = dalloc(w, &w->tile_work, 2 * (N / gw::COMBINED_TILE + 2))) ||
-        (rc = dalloc(w, &w->tile_order, 1 + (size_t)gw::combined_tiles((uint32_t)N) + 16)) || (rc = dalloc(w, &w->ework, N)) ||
-        (rc = dalloc(w, &w->nb_count, 1)))
+    if ((rc = gw::alloc_all(err, w->keys[0], N, w->keys[1], N, w->vals[0], N, w->vals[1], N, w->hist,
+                            gw::radix_hist_elems((uint32_t)N), w->si_lastop, N, w->si_rank, N, w->si_sp, N,
+                            w->new_slots_d, N, w->arr_idx, N, w->coll, N, w->blk, 3 * (N / 256 + 2), w->special,
+                            N / 256 + 2, w->tile_work, 2 * (N / gw::COMBINED_TILE + 2), w->tile_order,
+                            1 + (size_t)gw::combined_tiles((uint32_t)N) + 16, w->ework, N, w->nb_count, 1)))
         return fail(rc);
+    w->sinfo = gw::SlotTab{w->si_lastop, w->si_rank, w->si_sp};
     if (hipMemset(w->tile_order, 0, sizeof(uint32_t)) != hipSuccess ||  // no order yet
         hipMemset(w->ework, 0, N * sizeof(uint8_t)) != hipSuccess)
         return fail(GWAOI_EDEVICE);
@@ -1739,7 +1628,7 @@ int gwaoi_world_create(const gwaoi_config *cfg, gwaoi_world **out) {
     if (w->moves_bucketed && gw::moves_buckets((uint32_t)N) <= gw::MV_NB_MAX) {
         mv_hist_n = std::max(gw::moves_hist_elems((uint32_t)N, (uint32_t)N),
                              ((size_t)1 << 20) + 2 * (size_t)gw::moves_buckets((uint32_t)N) + 2);
-        if ((rc = dalloc(w, &w->mv_hist, mv_hist_n)) || (rc = dalloc(w, &w->mv_binned, N))) return fail(rc);
+        if ((rc = gw::alloc_all(err, w->mv_hist, mv_hist_n, w->mv_binned, N))) return fail(rc);
     }
     if ((rc = ensure_scan_tmp(w, std::max(gw::radix_hist_elems((uint32_t)N), mv_hist_n)))) return fail(rc);
     for (FlushSet &S : w->fs)
@@ -1750,11 +1639,8 @@ int gwaoi_world_create(const gwaoi_config *cfg, gwaoi_world **out) {
         if ((rc = ensure_events(w, S, cfg->event_capacity ? cfg->event_capacity : std::max<uint64_t>(4 * N, 1 << 16),
                                 cfg->event_capacity ? cfg->event_capacity : std::max<uint64_t>(4 * N, 1 << 16))))
             return fail(rc);
-    if (hipHostMalloc((void **)&w->h_grid, sizeof(SpaceGrid) * w->max_spaces, hipHostMallocDefault) != hipSuccess)
-        return fail(GWAOI_ENOMEM);
-    if (hipEventCreateWithFlags(&w->done_ev, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&w->order_ev, hipEventDisableTiming) != hipSuccess)
-        return fail(GWAOI_EDEVICE);
+    if (w->h_grid.alloc(w->max_spaces)) return fail(GWAOI_ENOMEM);
+    if (w->done_ev.create(hipEventDisableTiming) || w->order_ev.create(hipEventDisableTiming)) return fail(GWAOI_EDEVICE);
     w->alive.assign(N, 0);
     w->in_frame.assign(N, 0);
     w->appended.assign(N, 0);
@@ -1812,8 +1698,8 @@ int host_slots(gwaoi_world *w) {
     const DevFrame &F = w->fr[w->cur];
     std::vector<gw::SlotSp> ss(F.n);
     if (F.n) {
-        HIP_TRY(hipMemcpyAsync(ss.data(), F.ss, F.n * sizeof(gw::SlotSp), hipMemcpyDeviceToHost, w->stream));
-        HIP_TRY(hipStreamSynchronize(w->stream));
+        HIP_TRY(w->last_error, hipMemcpyAsync(ss.data(), F.ss, F.n * sizeof(gw::SlotSp), hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
     }
     std::fill(w->alive.begin(), w->alive.end(), 0);
     std::fill(w->in_frame.begin(), w->in_frame.end(), 0);
@@ -1900,26 +1786,21 @@ int ensure_stage(gwaoi_world *w, size_t words) {
     if (w->stage_used[h] + words <= w->stage_cap[h]) return GWAOI_OK;
     if (w->stage_used[h]) return 1;
     const size_t cap = std::max<size_t>({2 * words, 2 * w->stage_cap[h], (size_t)4 << 16});
-    HIP_TRY(hipStreamSynchronize(w->copy_st));  // no staging copy may still read the old buffer
-    if (w->h_stage[h]) (void)hipHostFree(w->h_stage[h]);
-    w->h_stage[h] = nullptr;
-    dfree(w->d_stage[h]);
-    w->stage_cap[h] = 0;
-    HIP_TRY(hipHostMalloc((void **)&w->h_stage[h], cap * sizeof(uint32_t), hipHostMallocDefault));
-    if (int rc = dalloc(w, &w->d_stage[h], cap)) return rc;
-    w->stage_cap[h] = cap;
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->copy_st));  // no staging copy may still read the old buffer
+    // a half's pinned and device buffers grow together, or the half is left empty
+    auto grow_half = [&](int q) {
+        w->stage_cap[q] = 0;
+        w->d_stage[q].reset();
+        int rc = gw::alloc_pinned(w->last_error, w->h_stage[q], cap);
+        if (!rc && (rc = gw::alloc_all(w->last_error, w->d_stage[q], cap))) w->h_stage[q].reset();
+        if (!rc) w->stage_cap[q] = cap;
+        return rc;
+    };
+    if (int rc = grow_half(h)) return rc;
     // grow the other half alike while no flush reads it, so that the first flush that stages
     // into it (the next one begun with gwaoi_tick_begin) does not pay the pinned allocation
     const int o = h ^ 1;
-    if (!w->in_flight && w->stage_used[o] == 0 && w->stage_cap[o] < cap) {
-        if (w->h_stage[o]) (void)hipHostFree(w->h_stage[o]);
-        w->h_stage[o] = nullptr;
-        dfree(w->d_stage[o]);
-        w->stage_cap[o] = 0;
-        if (hipHostMalloc((void **)&w->h_stage[o], cap * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess &&
-            dalloc(w, &w->d_stage[o], cap) == GWAOI_OK)
-            w->stage_cap[o] = cap;
-    }
+    if (!w->in_flight && w->stage_used[o] == 0 && w->stage_cap[o] < cap) (void)grow_half(o);
     return GWAOI_OK;
 }
 
@@ -2005,20 +1886,13 @@ int stage_moves(gwaoi_world *w, const uint32_t *slots, const float *x, const flo
     });
     for (unsigned t = 0; t < T; ++t)  // chunks are in call order: the first bad chunk has the first bad move
         if (st[t] != GWAOI_OK) return st[t];
-    HIP_TRY(hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(hipEventRecord(w->copy_ev, w->copy_st));
+    HIP_TRY(w->last_error, hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
+    HIP_TRY(w->last_error, hipEventRecord(w->copy_ev, w->copy_st));
     w->copy_pending = true;
     w->stage_used[half] += words;
-    Run r{};
-    r.device = true;
-    r.ds = d;
-    r.dx = reinterpret_cast<const float *>(d + n);
-    r.dz = reinterpret_cast<const float *>(d + 2 * n);
+    Run r = device_run(d, reinterpret_cast<const float *>(d + n), reinterpret_cast<const float *>(d + 2 * n), n);
     r.dsp = with_space ? d + 3 * n : nullptr;
-    r.seq0 = w->seq_next;
-    r.dn = n;
     r.checked = true;
-    w->seq_next += n;
     for (unsigned t = 0; t < T; ++t)
         for (size_t sp = 0; sp < nsp; ++sp) {
             const StageBox &b = boxes[(size_t)t * stride + sp];
@@ -2030,15 +1904,7 @@ int stage_moves(gwaoi_world *w, const uint32_t *slots, const float *x, const flo
                 note_pending_bbox(w->spaces[sp], b.x1, b.z1);
             }
         }
-    if (w->in_flight) {
-        Deferred q{};
-        q.kind = Deferred::RUN;
-        q.run = r;
-        w->deferred.push_back(q);
-    } else {
-        w->runs.push_back(r);
-        w->n_ops += n;
-    }
+    queue_run(w, r);
     return GWAOI_OK;
 }
 
@@ -2158,24 +2024,7 @@ int gwaoi_moved_batch_device(gwaoi_world *w, const uint32_t *d_slots, const floa
     if (!n) return GWAOI_OK;
     if (n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
     if (w->dev_seq_pending) return GWAOI_ESTATE;
-    Run r{};
-    r.device = true;
-    r.ds = d_slots;
-    r.dx = d_x;
-    r.dz = d_z;
-    r.dseq = nullptr;
-    r.seq0 = w->seq_next;
-    r.dn = n;
-    w->seq_next += n;
-    if (w->in_flight) {
-        Deferred q{};
-        q.kind = Deferred::RUN;
-        q.run = r;
-        w->deferred.push_back(q);
-        return GWAOI_OK;
-    }
-    w->runs.push_back(r);
-    w->n_ops += n;
+    queue_run(w, device_run(d_slots, d_x, d_z, n));
     return GWAOI_OK;
     });
 }
@@ -2188,16 +2037,9 @@ int gwaoi_moved_batch_device_seq(gwaoi_world *w, const uint32_t *d_slots, const 
     if (w->in_flight) return GWAOI_ESTATE;
     if (!n) return GWAOI_OK;
     if (n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
-    Run r{};
-    r.device = true;
-    r.ds = d_slots;
-    r.dx = d_x;
-    r.dz = d_z;
+    Run r = device_run(d_slots, d_x, d_z, n);
     r.dseq = reinterpret_cast<const unsigned long long *>(d_seq);
-    r.seq0 = 0;
-    r.dn = n;
-    w->runs.push_back(r);
-    w->n_ops += n;
+    queue_run(w, r);
     w->dev_seq_pending = true;
     return GWAOI_OK;
     });
@@ -2216,20 +2058,12 @@ int gwaoi_enter_batch_device(gwaoi_world *w, uint32_t space, const uint32_t *d_s
     if (box && !(std::isfinite(box[0]) && std::isfinite(box[1]) && std::isfinite(box[2]) && std::isfinite(box[3]) &&
                  box[0] <= box[2] && box[1] <= box[3]))
         return GWAOI_EINVAL;
-    Run r{};
-    r.device = true;
+    Run r = device_run(d_slots, d_x, d_z, n);
     r.kind = RUN_ENTER;
     r.space = space;
-    r.ds = d_slots;
-    r.dx = d_x;
-    r.dz = d_z;
     r.dseq = reinterpret_cast<const unsigned long long *>(d_seq);
-    r.seq0 = d_seq ? 0 : w->seq_next;
-    r.dn = n;
-    if (!d_seq) w->seq_next += n;
-    else w->dev_seq_pending = true;
-    w->runs.push_back(r);
-    w->n_ops += n;
+    queue_run(w, r);
+    if (d_seq) w->dev_seq_pending = true;
     w->dev_app += (uint32_t)n;
     w->dev_struct = true;
     w->space_ops_queued = true;
@@ -2252,17 +2086,12 @@ int gwaoi_leave_batch_device(gwaoi_world *w, uint32_t space, const uint32_t *d_s
     if (w->in_flight || w->sync) return GWAOI_ESTATE;
     if (!n) return GWAOI_OK;
     if (n > w->spaces[space].alive || n > 0xFFFFFFFFull - w->n_ops) return GWAOI_ESTATE;
-    Run r{};
-    r.device = true;
+    // a Leave has no position: the slot array stands in for x and z (read, never used)
+    const float *no_pos = reinterpret_cast<const float *>(d_slots);
+    Run r = device_run(d_slots, no_pos, no_pos, n);
     r.kind = RUN_LEAVE;
     r.space = space;
-    r.ds = d_slots;
-    // a Leave has no position: the slot array stands in for x and z (read, never used)
-    r.dx = r.dz = reinterpret_cast<const float *>(d_slots);
-    r.seq0 = w->seq_next;  // a Leave's seq is never compared
-    r.dn = n;
-    w->runs.push_back(r);
-    w->n_ops += n;
+    queue_run(w, r);
     w->dev_struct = true;
     w->space_ops_queued = true;
     w->n_alive -= (uint32_t)n;
@@ -2326,28 +2155,13 @@ int gwaoi_moved_batch_commit(gwaoi_world *w, size_t k) {
         }
     }
     const size_t words = (with_space ? 4 : 3) * n;
-    HIP_TRY(hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(hipEventRecord(w->copy_ev, w->copy_st));
+    HIP_TRY(w->last_error, hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
+    HIP_TRY(w->last_error, hipEventRecord(w->copy_ev, w->copy_st));
     w->copy_pending = true;
     w->stage_used[w->resv_half] += 4 * n;
-    Run r{};
-    r.device = true;
-    r.ds = d;
-    r.dx = reinterpret_cast<const float *>(d + n);
-    r.dz = reinterpret_cast<const float *>(d + 2 * n);
+    Run r = device_run(d, reinterpret_cast<const float *>(d + n), reinterpret_cast<const float *>(d + 2 * n), k);
     r.dsp = with_space ? d + 3 * n : nullptr;
-    r.seq0 = w->seq_next;
-    r.dn = k;
-    w->seq_next += k;
-    if (w->in_flight) {
-        Deferred q{};
-        q.kind = Deferred::RUN;
-        q.run = r;
-        w->deferred.push_back(q);
-    } else {
-        w->runs.push_back(r);
-        w->n_ops += k;
-    }
+    queue_run(w, r);
     return GWAOI_OK;
     });
 }
@@ -2369,29 +2183,13 @@ int gwaoi_moved_batch_pinned(gwaoi_world *w, const uint32_t *slots, const float 
     }
     const int h = w->stage_cur;
     uint32_t *d = w->d_stage[h] + w->stage_used[h];
-    HIP_TRY(hipMemcpyAsync(d, slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(hipMemcpyAsync(d + n, x, n * sizeof(float), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(hipMemcpyAsync(d + 2 * n, z, n * sizeof(float), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(hipEventRecord(w->copy_ev, w->copy_st));
+    HIP_TRY(w->last_error, hipMemcpyAsync(d, slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
+    HIP_TRY(w->last_error, hipMemcpyAsync(d + n, x, n * sizeof(float), hipMemcpyHostToDevice, w->copy_st));
+    HIP_TRY(w->last_error, hipMemcpyAsync(d + 2 * n, z, n * sizeof(float), hipMemcpyHostToDevice, w->copy_st));
+    HIP_TRY(w->last_error, hipEventRecord(w->copy_ev, w->copy_st));
     w->copy_pending = true;
     w->stage_used[h] += 3 * n;
-    Run r{};
-    r.device = true;
-    r.ds = d;
-    r.dx = reinterpret_cast<const float *>(d + n);
-    r.dz = reinterpret_cast<const float *>(d + 2 * n);
-    r.seq0 = w->seq_next;
-    r.dn = n;
-    w->seq_next += n;
-    if (w->in_flight) {
-        Deferred q{};
-        q.kind = Deferred::RUN;
-        q.run = r;
-        w->deferred.push_back(q);
-    } else {
-        w->runs.push_back(r);
-        w->n_ops += n;
-    }
+    queue_run(w, device_run(d, reinterpret_cast<const float *>(d + n), reinterpret_cast<const float *>(d + 2 * n), n));
     return GWAOI_OK;
     });
 }
@@ -2411,7 +2209,7 @@ int gwaoi_pinned_alloc(gwaoi_world *w, size_t bytes, void **out) {
 int gwaoi_pinned_free(gwaoi_world *w, void *p) {
     return gw::api_guard([&]() -> int {
     if (!w) return GWAOI_EINVAL;
-    if (p) HIP_TRY(hipHostFree(p));
+    if (p) HIP_TRY(w->last_error, hipHostFree(p));
     return GWAOI_OK;
     });
 }
@@ -2442,7 +2240,7 @@ void world_set_error(gwaoi_world *w, const char *msg) { w->last_error = msg; }
 void world_flush_events(gwaoi_world *w, const uint32_t **events, const uint32_t **dcount, uint64_t *cap) {
     FlushSet &S = w->fs[w->in_flight ? w->fl.set : w->last_set];
     *events = S.events;
-    *dcount = reinterpret_cast<const uint32_t *>(S.dev_out);
+    *dcount = reinterpret_cast<const uint32_t *>(S.dev_out.get());
     *cap = w->in_flight ? w->fl.cap.out : S.ev_cap;  // events the set's buffer holds (clipped to it)
 }
 
@@ -2458,17 +2256,9 @@ int world_queue_decoded(gwaoi_world *w, const uint32_t *d_slots, const float *d_
     if (!n) return GWAOI_OK;
     if (n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
     if (w->dev_seq_pending) return GWAOI_ESTATE;
-    Run r{};
-    r.device = true;
-    r.ds = d_slots;
-    r.dx = d_x;
-    r.dz = d_z;
+    Run r = device_run(d_slots, d_x, d_z, n);
     r.dsp = d_sp;
-    r.seq0 = w->seq_next;
-    r.dn = n;
-    w->runs.push_back(r);
-    w->n_ops += n;
-    w->seq_next += n;
+    queue_run(w, r);
     return GWAOI_OK;
 }
 
@@ -2540,15 +2330,15 @@ int copy_out(gwaoi_world *w, bool pairs, uint64_t regrows) {
     if (tot) {
         // ordered after the flush's last kernel (its event's release makes the writes visible to the
         // copy engine); after a re-run of its pair passes, after the wait that followed the re-run
-        HIP_TRY(hipStreamWaitEvent(w->out_st, w->dbg.event_regrows != regrows ? w->done_ev : S.done_ev, 0));
+        HIP_TRY(w->last_error, hipStreamWaitEvent(w->out_st, w->dbg.event_regrows != regrows ? w->done_ev : S.done_ev, 0));
         if (pairs) {
-            gw::launch_pairs_out(S.events, tot / 2, w->d_h_events, w->out_st);
-            HIP_TRY(hipGetLastError());
+            gw::launch_pairs_out(S.events, tot / 2, w->h_events.dev(), w->out_st);
+            HIP_TRY(w->last_error, hipGetLastError());
         } else {
-            HIP_TRY(hipMemcpyAsync(w->h_events, S.events, 2 * tot * sizeof(uint32_t), hipMemcpyDeviceToHost,
+            HIP_TRY(w->last_error, hipMemcpyAsync(w->h_events, S.events, 2 * tot * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                    w->out_st));
         }
-        HIP_TRY(hipEventRecord(w->out_ev, w->out_st));
+        HIP_TRY(w->last_error, hipEventRecord(w->out_ev, w->out_st));
         w->out_pending = true;
     }
     return GWAOI_OK;
@@ -2709,7 +2499,7 @@ int gwaoi_tick(gwaoi_world *w, gwaoi_events *out) {
         w->out_n_enter = w->last_n_enter;
         w->out_n_leave = w->last_n_leave;
         if (tot) {
-            HIP_TRY(hipMemcpyAsync(w->h_events, w->fs[w->last_set].events, 2 * tot * sizeof(uint32_t),
+            HIP_TRY(w->last_error, hipMemcpyAsync(w->h_events, w->fs[w->last_set].events, 2 * tot * sizeof(uint32_t),
                                    hipMemcpyDeviceToHost, w->stream));
             if (int rw = wait_stream(w)) return poison(w, rw);
         }
@@ -2742,24 +2532,19 @@ int build_csr(gwaoi_world *w) {
     const uint64_t tot = w->last_n_enter + w->last_n_leave;
     if (w->csr_tick == w->ticks) return GWAOI_OK;
     const size_t rows = w->max_slots;
-    if (!w->csr_cnt) {
-        int rc;
-        if ((rc = dalloc(w, &w->csr_cnt, rows + 1)) || (rc = dalloc(w, &w->csr_off, rows + 1)) ||
-            (rc = dalloc(w, &w->csr_long, rows)))
-            return rc;
-    }
+    if (!w->csr_cnt)
+        if (int rc = gw::alloc_all(w->last_error, w->csr_cnt, rows + 1, w->csr_off, rows + 1, w->csr_long, rows)) return rc;
     if (tot > w->csr_items_cap) {
-        HIP_TRY(hipStreamSynchronize(w->stream));
-        dfree(w->csr_items);
+        HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
         w->csr_items_cap = 0;
         const uint64_t cap = std::max<uint64_t>(tot + tot / 4, 1 << 16);
-        if (int rc = dalloc(w, &w->csr_items, 2 * cap)) return rc;  // items | merge scratch of long rows
+        if (int rc = gw::alloc_all(w->last_error, w->csr_items, 2 * cap)) return rc;  // items | merge scratch of long rows
         w->csr_items_cap = cap;
     }
     if (int rc = ensure_scan_tmp(w, rows + 1)) return rc;
     gw::launch_events_csr(last_events(w), w->last_n_enter, tot, (uint32_t)rows, w->csr_cnt, w->csr_off, w->scan_tmp,
                           w->csr_items, w->csr_items + w->csr_items_cap, w->csr_long, w->stream);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(w->last_error, hipGetLastError());
     w->csr_tick = w->ticks;
     return GWAOI_OK;
 }
@@ -2786,18 +2571,13 @@ int gwaoi_events_csr(gwaoi_world *w, const uint32_t **offsets, const uint32_t **
     if (w->in_flight) return GWAOI_ESTATE;
     if (int rc = build_csr(w)) return rc;
     const uint64_t tot = w->last_n_enter + w->last_n_leave;
-    if (!w->h_csr_off) HIP_TRY(hipHostMalloc((void **)&w->h_csr_off, ((size_t)w->max_slots + 1) * 4, hipHostMallocDefault));
-    if (tot > w->h_csr_items_cap) {
-        if (w->h_csr_items) (void)hipHostFree(w->h_csr_items);
-        w->h_csr_items = nullptr;
-        w->h_csr_items_cap = 0;
-        const uint64_t cap = std::max<uint64_t>(tot + tot / 4, 1 << 16);
-        HIP_TRY(hipHostMalloc((void **)&w->h_csr_items, cap * 4, hipHostMallocDefault));
-        w->h_csr_items_cap = cap;
-    }
+    if (!w->h_csr_off)
+        if (int rc = gw::alloc_pinned(w->last_error, w->h_csr_off, (size_t)w->max_slots + 1)) return rc;
+    if (tot > w->h_csr_items.cap())
+        if (int rc = gw::alloc_pinned(w->last_error, w->h_csr_items, std::max<uint64_t>(tot + tot / 4, 1 << 16))) return rc;
     w->gen++;
-    HIP_TRY(hipMemcpyAsync(w->h_csr_off, w->csr_off, ((size_t)w->max_slots + 1) * 4, hipMemcpyDeviceToHost, w->stream));
-    if (tot) HIP_TRY(hipMemcpyAsync(w->h_csr_items, w->csr_items, tot * 4, hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(w->last_error, hipMemcpyAsync(w->h_csr_off, w->csr_off, ((size_t)w->max_slots + 1) * 4, hipMemcpyDeviceToHost, w->stream));
+    if (tot) HIP_TRY(w->last_error, hipMemcpyAsync(w->h_csr_items, w->csr_items, tot * 4, hipMemcpyDeviceToHost, w->stream));
     if (int rc = wait_stream(w)) return rc;
     *offsets = w->h_csr_off;
     *items = w->h_csr_items;
@@ -2816,25 +2596,21 @@ int gwaoi_neighbors(gwaoi_world *w, uint32_t slot, uint32_t *out, size_t cap, si
     if (int rc = host_slots(w)) return rc;
     if (!w->in_frame[slot]) return GWAOI_ESTATE;
     const size_t need = std::max<size_t>(cap, 1);
-    if (need > w->nb_cap) {
-        dfree(w->nb_out);
-        int rc = dalloc(w, &w->nb_out, need);
-        if (rc) return rc;
-        w->nb_cap = need;
-    }
+    if (need > w->nb_out.cap())
+        if (int rc = gw::alloc_all(w->last_error, w->nb_out, need)) return rc;
     const DevFrame &F = w->fr[w->cur];
     w->gen++;
-    HIP_TRY(hipMemsetAsync(w->nb_count, 0, sizeof(uint32_t), w->stream));
+    HIP_TRY(w->last_error, hipMemsetAsync(w->nb_count, 0, sizeof(uint32_t), w->stream));
     gw::launch_neighbors(view_of(F), w->sinfo, slot, w->nb_out, (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu),
                          w->nb_count, w->stream);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(w->last_error, hipGetLastError());
     uint32_t cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, w->nb_count, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-    HIP_TRY(hipStreamSynchronize(w->stream));
+    HIP_TRY(w->last_error, hipMemcpyAsync(&cnt, w->nb_count, sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
     const size_t k = std::min<size_t>(cnt, cap);
     if (k) {
-        HIP_TRY(hipMemcpyAsync(out, w->nb_out, k * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
-        HIP_TRY(hipStreamSynchronize(w->stream));
+        HIP_TRY(w->last_error, hipMemcpyAsync(out, w->nb_out, k * sizeof(uint32_t), hipMemcpyDeviceToHost, w->stream));
+        HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
     }
     if (n_out) *n_out = cnt;
     return GWAOI_OK;
@@ -2854,9 +2630,9 @@ int gwaoi_snapshot(gwaoi_world *w, uint32_t *slots, uint32_t *spaces, float *x, 
     std::vector<gw::Rec16> rec(F.n);
     std::vector<gw::SlotSp> ss(F.n);
     w->gen++;
-    HIP_TRY(hipMemcpyAsync(rec.data(), F.rec, F.n * sizeof(gw::Rec16), hipMemcpyDeviceToHost, w->stream));
-    HIP_TRY(hipMemcpyAsync(ss.data(), F.ss, F.n * sizeof(gw::SlotSp), hipMemcpyDeviceToHost, w->stream));
-    HIP_TRY(hipStreamSynchronize(w->stream));
+    HIP_TRY(w->last_error, hipMemcpyAsync(rec.data(), F.rec, F.n * sizeof(gw::Rec16), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(w->last_error, hipMemcpyAsync(ss.data(), F.ss, F.n * sizeof(gw::SlotSp), hipMemcpyDeviceToHost, w->stream));
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
     for (uint32_t i = 0; i < F.n; ++i) {
         slots[i] = ss[i].slot;
         spaces[i] = ss[i].sp;
@@ -2965,7 +2741,7 @@ int gwaoi_reset_stage_times(gwaoi_world *w) {
 int gwaoi_sync(gwaoi_world *w) {
     return gw::api_guard([&]() -> int {
     if (!w) return GWAOI_EINVAL;
-    HIP_TRY(hipStreamSynchronize(w->stream));
+    HIP_TRY(w->last_error, hipStreamSynchronize(w->stream));
     return GWAOI_OK;
     });
 }
@@ -2979,8 +2755,8 @@ void *gwaoi_stream(gwaoi_world *w) {
 int gwaoi_stream_after(gwaoi_world *w, void *other) {
     return gw::api_guard([&]() -> int {
     if (!w) return GWAOI_EINVAL;
-    HIP_TRY(hipEventRecord(w->order_ev, (hipStream_t)other));
-    HIP_TRY(hipStreamWaitEvent(w->stream, w->order_ev, 0));
+    HIP_TRY(w->last_error, hipEventRecord(w->order_ev, (hipStream_t)other));
+    HIP_TRY(w->last_error, hipStreamWaitEvent(w->stream, w->order_ev, 0));
     w->gen++;  // the next flush's early kernels wait for the other stream too
     return GWAOI_OK;
     });
@@ -2989,8 +2765,8 @@ int gwaoi_stream_after(gwaoi_world *w, void *other) {
 int gwaoi_stream_before(gwaoi_world *w, void *other) {
     return gw::api_guard([&]() -> int {
     if (!w) return GWAOI_EINVAL;
-    HIP_TRY(hipEventRecord(w->order_ev, w->stream));
-    HIP_TRY(hipStreamWaitEvent((hipStream_t)other, w->order_ev, 0));
+    HIP_TRY(w->last_error, hipEventRecord(w->order_ev, w->stream));
+    HIP_TRY(w->last_error, hipStreamWaitEvent((hipStream_t)other, w->order_ev, 0));
     return GWAOI_OK;
     });
 }

@@ -63,6 +63,17 @@ def test_pure_host_entry_points(lib):
     assert lib.gwaoi_wire_set_clients(None, None, None, 0) == -1
 
 
+def test_world_create_without_device(lib):
+    """gwaoi_world_create on a device that is not there: GWAOI_EDEVICE, *out == NULL, and the
+    half-built world released.  On a machine without a GPU that is the default device; where one
+    is present, a device index no machine has takes the same early path."""
+    have_gpu = os.path.exists("/dev/kfd")
+    cfg = _lib.Config(4096, 1, (1 << 20) if have_gpu else -1, 0, 0, 0.0)
+    out = C.c_void_p(1)
+    assert lib.gwaoi_world_create(C.byref(cfg), C.byref(out)) == -5  # GWAOI_EDEVICE
+    assert out.value is None
+
+
 def test_library_is_gfx950_code_object():
     path = _lib.LIB_PATH
     data = open(path, "rb").read()

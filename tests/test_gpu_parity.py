@@ -1290,6 +1290,89 @@ def test_cell_size_switch_keeps_parity_gpu(oracle_mod):
         assert B.debug_counters()["cell_size_switches"] == 0
 
 
+def test_buffer_growths_then_second_world_gpu(oracle_mod):
+    """Every host-side growth path once, in one sequence checked against the closed form at
+    every flush, on a 4,096-slot world created with event_capacity=1024:
+    the event buffers (the first flush's enters alone exceed 1,024 events), the cell array (the
+    crowd covers more than the 1,024 cells allocated at creation, then nine times the area), the
+    host op queue (1,500 single Moved calls in one flush against the 1,024 ops allocated at
+    creation; every flush before it queues at most 1,024), the staging area (one 2,000-move
+    batch, above the staging threshold of 64 moves, into staging memory that starts empty) and
+    the incremental sort's arrays (a flush on the unchanged, grown grid).  The world is then
+    destroyed, and a second world created in the same process runs one correct tick."""
+    n, chunk = 4096, 1024
+    rng = np.random.default_rng(77)
+    x = rng.uniform(0, 3000, n).astype(np.float32)
+    z = rng.uniform(0, 3000, n).astype(np.float32)
+    seq = np.zeros(n, np.uint64)
+    sp = np.full(n, oracle_mod.DEAD, np.uint32)
+    state = {"prev": np.empty(0, np.uint64), "nxt": 1}
+
+    def check(w, what):
+        ge, gl = flush(w)
+        cur = oracle_mod.closed_form_pairs(x, z, seq, sp, {0: D})
+        np.testing.assert_array_equal(ge, np.setdiff1d(cur, state["prev"]), err_msg=f"{what}: enters")
+        np.testing.assert_array_equal(gl, np.setdiff1d(state["prev"], cur), err_msg=f"{what}: leaves")
+        state["prev"] = cur
+
+    def stamp(slots):  # the calls just made took the next seqs in call order
+        seq[slots] = state["nxt"] + np.arange(len(slots), dtype=np.uint64)
+        state["nxt"] += len(slots)
+
+    with World(n, event_capacity=1024, cells_per_dist=3.0) as w:  # (a fixed cell size: only the extent changes)
+        s = w.space_create(D)
+        cap0 = w.info()["event_capacity"]  # (the requested 1,024 plus the growth slack of a quarter)
+        assert cap0 < 2048
+        for c in range(n // chunk):  # at most 1,024 queued ops per flush: the op queue does not grow yet
+            ids = np.arange(c * chunk, (c + 1) * chunk, dtype=np.uint32)
+            for i in ids:
+                w.enter(s, int(i), x[i], z[i])
+            sp[ids] = 0
+            stamp(ids)
+            check(w, f"enter chunk {c}")
+        cells0 = w.info()["total_cells"]
+        print("event_capacity", w.info()["event_capacity"], "regrows", w.debug_counters()["event_regrows"],
+              "cells", cells0)
+        assert w.debug_counters()["event_regrows"] >= 1 and w.info()["event_capacity"] > cap0
+        assert cells0 > 1024
+        # the host op queue: 1,500 single Moved calls in one flush
+        ids = rng.permutation(n)[:1500].astype(np.uint32)
+        x[ids] += rng.uniform(-30, 30, ids.size).astype(np.float32)
+        z[ids] += rng.uniform(-30, 30, ids.size).astype(np.float32)
+        for i in ids:
+            w.moved(int(i), x[i], z[i])
+        stamp(ids)
+        check(w, "1500 single moves")
+        # the staging area, and the cell array again: a staged batch that triples the crowd's extent
+        ids = rng.permutation(n)[:2000].astype(np.uint32)
+        x[ids] = (x[ids] * np.float32(3.0)).astype(np.float32)
+        z[ids] = (z[ids] * np.float32(3.0)).astype(np.float32)
+        w.moved_batch(ids, x[ids], z[ids])
+        stamp(ids)
+        check(w, "staged batch")
+        cells1 = w.info()["total_cells"]
+        print("cells after the spread", cells1)
+        assert cells1 > 2 * cells0
+        # the incremental sort on the grown grid (small moves keep the grid)
+        inc0 = w.debug_counters()["incremental_sorts"]
+        ids = np.arange(n, dtype=np.uint32)
+        x += rng.uniform(-1, 1, n).astype(np.float32)
+        z += rng.uniform(-1, 1, n).astype(np.float32)
+        w.moved_batch(ids, x, z)
+        stamp(ids)
+        check(w, "jitter")
+        assert w.debug_counters()["incremental_sorts"] > inc0
+    # a second world in the same process, after the first released everything it held
+    with World(n, event_capacity=1024) as w:
+        s = w.space_create(D)
+        ids = np.arange(n, dtype=np.uint32)
+        w.enter_batch(s, ids, x, z)
+        seq[:] = 1 + np.arange(n, dtype=np.uint64)
+        state["prev"] = np.empty(0, np.uint64)
+        check(w, "second world")
+        assert w.info()["live"] == n
+
+
 def test_device_enter_leave_batches_match_host_calls_gpu(oracle_mod):
     """gwaoi_enter_batch_device / gwaoi_leave_batch_device (the strip worlds' boundary
     crossers, Space.go:211,243) give the events of the same Enter/Leave calls made on the
