@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libgwaoi.so")
 SOURCES = ["gwaoi_kernels.hip", "gwaoi_world.cpp", "gwaoi_strips.hip", "gwaoi_sync.hip", "gwaoi_wire.hip",
            "gwaoi_sparse.hip"]
-HEADERS = ["gwaoi_internal.h", "gwaoi_device.h", "gwaoi_mem.h", os.path.join("..", "..", "include", "gwaoi.h"),
+HEADERS = ["gwaoi_internal.h", "gwaoi_device.h", "gwaoi_mem.h", "gwaoi_plan.h", os.path.join("..", "..", "include", "gwaoi.h"),
            os.path.join("..", "..", "include", "gwaoi_sync.h"),
            os.path.join("..", "..", "include", "gwaoi_strips.h"), os.path.join("..", "..", "include", "gwaoi_wire.h")]
 
@@ -88,6 +88,26 @@ def build_mem_test(force: bool = False, verbose: bool = False) -> str:
     return MEM_TEST_OUT
 
 
+PLAN_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "plan_test.cpp")
+PLAN_TEST_OUT = os.path.join(HERE, "lib", "plan_test")
+
+
+def build_plan_test(force: bool = False, verbose: bool = False) -> str:
+    """Stand-alone host test of csrc/gwaoi_plan.h (the flush's decisions): the header alone, plain g++."""
+    deps = [PLAN_TEST_SRC, os.path.join(CSRC, "gwaoi_plan.h")]
+    if (not force and os.path.exists(PLAN_TEST_OUT)
+            and all(os.path.getmtime(d) <= os.path.getmtime(PLAN_TEST_OUT) for d in deps)):
+        return PLAN_TEST_OUT
+    os.makedirs(os.path.dirname(PLAN_TEST_OUT), exist_ok=True)
+    tmp = PLAN_TEST_OUT + ".tmp"
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-I", CSRC, PLAN_TEST_SRC, "-o", tmp]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(tmp, PLAN_TEST_OUT)
+    return PLAN_TEST_OUT
+
+
 TICK_BENCH_SRC =os.path.join(ROOT, "tools", "tick_bench.cpp")
 TICK_BENCH_OUT = os.path.join(HERE, "lib", "gwaoi_tick_bench")
 
@@ -115,3 +135,4 @@ if __name__ == "__main__":
     print(build_cpp_tests(verbose=True))
     print(build_tick_bench(verbose=True))
     print(build_mem_test(verbose=True))
+    print(build_plan_test(verbose=True))

@@ -9,6 +9,8 @@
 
 #include <new>
 
+#include "gwaoi_plan.h"
+
 struct gwaoi_world;  // include/gwaoi.h
 
 namespace gw {
@@ -169,9 +171,8 @@ void launch_ops_apply(const uint32_t *slots, const float *x, const float *z, con
                       uint32_t n, uint32_t j0, uint32_t max_slots, SlotTab info, uint32_t tick_id,
                       uint32_t n_total, const unsigned long long *seqs, uint64_t seq0, uint64_t seq_floor,
                       bool track_max, Rec16 *s_rec, SlotSp *s_ss, TickScalars *sc, hipStream_t st);
-// A flush whose queue is only device Moved batches (<= MAX_MOVE_RUNS of them):
+// A flush whose queue is only device Moved batches (<= MAX_MOVE_RUNS of them, gwaoi_plan.h):
 // single-pass claim+apply, then a fixup of the slots moved more than once.
-constexpr uint32_t MAX_MOVE_RUNS = 4;
 struct MoveRun {
     const uint32_t *ds;
     const float *dx, *dz;
@@ -260,9 +261,9 @@ void launch_keygen(Rec16 *s_rec, const SlotSp *s_ss, uint32_t n_total, const Spa
 // words (the cell scan's tile totals);
 // arr_pos: 3 (total_cells + 1) words (arrival cursors, per-cell shifts, changed cells).
 size_t incr_sort_tmp_elems(size_t cells);
-// true: the sort leaves cnt64 zero for the next flush (zeroed once when allocated)
-bool scan_rezeroes_counts();
-// The special pass (launch_pairs' arguments), run inside the incremental sort's arrival launch
+// (the sort leaves cnt64 zero for the next flush: zeroed once when allocated, then k_arrive re-zeroes
+// the counted cells)
+// The special pass: launch_pairs runs it, or the incremental sort's arrival launch
 // (k_arrive_special) when sp != nullptr; n_tiles = the previous frame's tiles.
 struct SpecialJob {
     FrameView F;
@@ -278,7 +279,7 @@ struct SpecialJob {
     const uint32_t *special;
     uint32_t n_tiles;
 };
-// The gather (launch_gather's arguments), run inside the incremental sort's merge launch
+// The gather: launch_gather runs it, or the incremental sort's merge launch
 // (k_merge_gather) when gj != nullptr: block b gathers scan tile b's range of the new frame once it
 // has merged the tile's changed cells, and writes bbox part b (incr_sort_tiles parts, which
 // launch_finish folds).  The sort's perm / skeys are the gather's.
@@ -322,11 +323,9 @@ size_t scan_tmp_elems(size_t n);
 
 // New frame (f_rec/f_ss), previous state in the new order (o_rec), and the
 // combined pass's candidate records cand = {x, z, old x, old z} (x, z NaN for a jumper).
-void launch_gather(const uint32_t *perm, uint32_t n_new, uint32_t n_prev, const Rec16 *s_rec, const SlotSp *s_ss,
-                   const Rec16 *p_rec, const SlotSp *p_ss, Rec16 *f_rec, SlotSp *f_ss, Rec16 *o_rec, uint4 *cand,
-                   const SpaceGrid *grid, uint64_t seq_base, SlotTab info, const uint32_t *sorted_keys,
-                   uint32_t sentinel, uint32_t n_total, TickScalars *sc, uint32_t *f_key, int4 *bbox,
-                   uint32_t n_spaces, void *bbox_parts, hipStream_t st);
+// perm / sorted_keys: the sort's outputs; f_key (optional): the frame's keys, written from sorted_keys.
+void launch_gather(const GatherJob &G, const uint32_t *perm, const uint32_t *sorted_keys, uint32_t sentinel,
+                   uint32_t n_total, uint32_t *f_key, uint64_t seq_base, hipStream_t st);
 void launch_cell_count(const uint32_t *sorted_keys, uint32_t n, uint32_t *cnt, hipStream_t st);
 
 // Combined pass over the new frame: blocks of TILE_A consecutive entries
@@ -351,10 +350,9 @@ void launch_combined(FrameView F, const uint4 *cand, const Rec16 *O_rec, uint64_
 // otherwise).  launch_finish builds it for the next flush when given the buffers.
 // Special-entity pass over the previous frame in blocks of TILE_A entries
 // (O = S', the new state in the previous order, with O_ss giving its space);
-// block t's totals/bases at [tile_off + t] and [leave_off + tile_off + t].
-void launch_pairs(FrameView F, const Rec16 *O_rec, const SlotSp *O_ss, uint64_t seq_base, TickScalars *sc,
-                  uint32_t *tmp_pairs, uint64_t cap, uint32_t *tile_total, unsigned long long *tile_base,
-                  uint32_t tile_off, uint32_t leave_off, const uint32_t *special, hipStream_t st);
+// block t's totals/bases at [tile_off + t] and [leave_off + tile_off + t].  J.special == nullptr:
+// every tile is visited.
+void launch_pairs(const SpecialJob &J, hipStream_t st);
 // The flush's tail in one launch: every tile's events from tmp into tile order
 // (`out` may be host-mapped pinned memory, and hbbox, when given, receives the
 // folded per-space boxes there: the flush summary needs no copy)

@@ -3378,9 +3378,6 @@ void launch_keygen(Rec16 *s_rec, const SlotSp *s_ss, uint32_t n_total, const Spa
     }
 }
 
-// k_arrive re-zeroes the counted cells (no clearing pass over cnt64)
-bool scan_rezeroes_counts() { return true; }
-
 size_t incr_sort_tmp_elems(size_t cells) { return 2 * ((size_t)cdiv(cells + 1, S64_TILE) + 1); }  // tile totals, counts
 
 void incremental_sort(const uint32_t *keys, uint32_t n_total, uint32_t n_prev, const uint32_t *p_key,
@@ -3454,15 +3451,12 @@ int radix_sort(SortBuffers &b, uint32_t n, int bits, hipStream_t st) {
     return cur;
 }
 
-void launch_gather(const uint32_t *perm, uint32_t n_new, uint32_t n_prev, const Rec16 *s_rec, const SlotSp *s_ss,
-                   const Rec16 *p_rec, const SlotSp *p_ss, Rec16 *f_rec, SlotSp *f_ss, Rec16 *o_rec, uint4 *cand,
-                   const SpaceGrid *grid, uint64_t seq_base, SlotTab info, const uint32_t *sorted_keys,
-                   uint32_t sentinel, uint32_t n_total, TickScalars *sc, uint32_t *f_key, int4 *bbox,
-                   uint32_t n_spaces, void *bbox_parts, hipStream_t st) {
-    const uint32_t nt = std::max<uint32_t>(n_new, 1u);
-    k_gather<<<cdiv(nt, 256), 256, 0, st>>>(perm, n_new, n_prev, s_rec, s_ss, p_rec, p_ss, f_rec, f_ss, o_rec, cand,
-                                            grid, seq_base, info, sorted_keys, sentinel, n_total, sc, f_key, bbox,
-                                            n_spaces, reinterpret_cast<BBoxPart *>(bbox_parts));
+void launch_gather(const GatherJob &G, const uint32_t *perm, const uint32_t *sorted_keys, uint32_t sentinel,
+                   uint32_t n_total, uint32_t *f_key, uint64_t seq_base, hipStream_t st) {
+    const uint32_t nt = std::max<uint32_t>(G.n_new, 1u);
+    k_gather<<<cdiv(nt, 256), 256, 0, st>>>(perm, G.n_new, G.n_prev, G.s_rec, G.s_ss, G.p_rec, G.p_ss, G.f_rec, G.f_ss,
+                                            G.o_rec, G.cand, G.grid, seq_base, G.info, sorted_keys, sentinel, n_total,
+                                            G.sc, f_key, G.bbox, G.n_spaces, reinterpret_cast<BBoxPart *>(G.parts));
 }
 
 void launch_cell_count(const uint32_t *sorted_keys, uint32_t n, uint32_t *cnt, hipStream_t st) {
@@ -3470,13 +3464,10 @@ void launch_cell_count(const uint32_t *sorted_keys, uint32_t n, uint32_t *cnt, h
     k_cell_count<<<cdiv(n, 256), 256, 0, st>>>(sorted_keys, n, cnt);
 }
 
-void launch_pairs(FrameView F, const Rec16 *O_rec, const SlotSp *O_ss, uint64_t seq_base, TickScalars *sc,
-                  uint32_t *tmp_pairs, uint64_t cap, uint32_t *tile_total, unsigned long long *tile_base,
-                  uint32_t tile_off, uint32_t leave_off, const uint32_t *special, hipStream_t st) {
-    if (!F.n) return;
-    uint2 *tmp = reinterpret_cast<uint2 *>(tmp_pairs);
-    k_pairs<1><<<combined_blocks(F.n), PT, 0, st>>>(F, O_rec, O_ss, seq_base, sc, sc, tmp, cap, tile_total,
-                                                    tile_base, tile_off, leave_off, sc->dbg, special);
+void launch_pairs(const SpecialJob &J, hipStream_t st) {
+    if (!J.n_tiles) return;
+    k_pairs<1><<<J.n_tiles, PT, 0, st>>>(J.F, J.O_rec, J.O_ss, J.seq_base, J.sc, J.sc, J.tmp, J.cap, J.tile_total,
+                                         J.tile_base, J.tile_off, J.leave_off, J.sc->dbg, J.special);
 }
 
 void launch_combined(FrameView F, const uint4 *cand, const Rec16 *O_rec, uint64_t seq_base, TickScalars *sc,

@@ -40,7 +40,7 @@ using gw::SpaceGrid;
 
 namespace {
 
-enum Stage { ST_APPLY, ST_KEYGEN, ST_SORT, ST_GATHER, ST_CELLS, ST_COMBINED, ST_SPECIAL, ST_FINISH, ST_D2H, ST_N };
+using namespace gw::stages;  // Stage, ST_* (gwaoi_plan.h)
 const char *kStageNames[ST_N] = {"apply",    "keygen",  "sort",   "gather", "cells",
                                  "combined", "special", "finish", "d2h"};
 
@@ -248,7 +248,6 @@ struct gwaoi_world {
     gw::DevBuf<uint8_t> ework;        // per frame entry: log2 of the candidates its lane swept (the next flush's deal)
     gw::DevBuf<uint32_t> mv_hist;  // bucketed apply: the bucket-major histogram, scanned (gw::launch_moves_bucketed)
     gw::DevBuf<uint4> mv_binned;  // bucketed apply: the ops regrouped by slot bucket (16 B each)
-    bool moves_bucketed = false;   // the bucketed apply (max_slots > MV_MIN_SLOTS; GWAOI_MOVES_BUCKETED forces it)
     // test and diagnostics flags (GWAOI_F_TEST_*, include/gwaoi.h)
     bool force_radix = false;  // always the full radix sort (checks the incremental sort against it)
     bool force_copy = false;   // S' always copied by the prologue (checks virtual S' against it)
@@ -356,14 +355,12 @@ struct gwaoi_world {
     // deferred, then queued for the next flush.
     bool in_flight = false;
     struct Flight {
-        uint32_t tick_id;
-        size_t entries;
+        // how it was launched: its set, frames, seq floor and entries, and every decision of it.
+        // plan.sp_fused records whether its special pass rode on the sort; nothing reads that yet
+        // ("The flush plan": known gap)
+        gw::FlushPlan plan;
         uint64_t seq_next;  // seq_next when the flush's queue was closed (the next flush's floor)
-        uint64_t seq_base;  // the flush's seq floor (every seq of it is >= seq_base)
         bool dev_seq;       // it held an explicit-seq device batch
-        int set;            // FlushSet it writes
-        int p_idx, n_idx;   // previous / new frame
-        const gw::SlotSp *s_ss_view;  // its S' spaces: the set's sss, or the previous frame's (virtual S')
         EvCaps cap;         // event capacities its pair passes were launched with (writes clipped to them)
         std::vector<uint8_t> touched_alive;  // liveness of touched[i] when the queue was closed
     } fl;
@@ -757,14 +754,7 @@ void choose_grids(gwaoi_world *w, uint32_t &total_cells, uint32_t &total_rows) {
 }
 
 gw::FrameView view_of(const DevFrame &f) {
-    gw::FrameView v;
-    v.rec = f.rec;
-    v.ss = f.ss;
-    v.cell_start = f.cell_start;
-    v.grid = f.grid;
-    v.n = f.n;
-    v.total_cells = f.total_cells;
-    return v;
+    return gw::FrameView{f.rec, f.ss, f.cell_start, f.grid, f.n, f.total_cells};
 }
 
 int bitlen(uint32_t v) {
@@ -785,6 +775,36 @@ int4 *dev_bbox(FlushSet &S) { return reinterpret_cast<int4 *>(S.dev_out + kDevBB
 // the events of the last committed flush
 uint32_t *last_events(gwaoi_world *w) { return w->fs[w->last_set].events; }
 
+// ---- the flush: tick_launch gathers the facts, makes room, decides everything at once
+// (gw::plan_flush, gwaoi_plan.h) and queues the stages below in order.  P: the previous flush's
+// frame, Fn: the one this flush writes, S: its flush set, st: the stream of its early kernels.
+
+// The flush's S' spaces: the set's, or the previous frame's (virtual S').
+const gw::SlotSp *s_ss_view(const FlushSet &S, const DevFrame &P, const gw::FlushPlan &plan) {
+    return plan.virt ? P.ss : S.sss;
+}
+
+// The special pass: for the sort's arrival launch when it rides there (plan.sp_fused), else launch_pairs.
+gw::SpecialJob special_job(gwaoi_world *w, FlushSet &S, const DevFrame &P, const DevFrame &Fn, const gw::FlushPlan &plan) {
+    const uint32_t TBn = gw::combined_tiles(Fn.n), TBp = gw::combined_blocks(P.n);
+    gw::SpecialJob J{};
+    J.F = view_of(P); J.O_rec = S.srec; J.O_ss = s_ss_view(S, P, plan);
+    J.seq_base = plan.seq_base; J.sc = S.sc; J.tmp = reinterpret_cast<uint2 *>(S.evtmp.get()); J.cap = S.evtmp_cap;
+    J.tile_total = S.tile_total; J.tile_base = S.tile_base; J.tile_off = TBn; J.leave_off = TBn + TBp;
+    J.special = w->special; J.n_tiles = TBp;
+    return J;
+}
+
+// The gather: for the sort's merge launch when it rides there (plan.ga_fused), else launch_gather.
+gw::GatherJob gather_job(gwaoi_world *w, FlushSet &S, const DevFrame &P, DevFrame &Fn, const gw::FlushPlan &plan) {
+    gw::GatherJob G{};
+    G.n_new = plan.n_new; G.n_prev = P.n; G.s_rec = S.srec; G.s_ss = s_ss_view(S, P, plan); G.p_rec = P.rec; G.p_ss = P.ss;
+    G.f_rec = Fn.rec; G.f_ss = Fn.ss; G.o_rec = S.orec; G.cand = S.cand;
+    G.grid = Fn.grid; G.info = w->sinfo; G.sc = S.sc;
+    G.bbox = dev_bbox(S); G.n_spaces = w->n_space_ids; G.parts = S.bbox_parts;
+    return G;
+}
+
 // Pair passes + deterministic reorder.  Block-total entries: [enter totals:
 // new-frame blocks | previous-frame blocks] then [leave totals: same order];
 // their exclusive scan is the final layout [enters | leaves] in block order.
@@ -796,28 +816,24 @@ uint32_t *last_events(gwaoi_world *w) { return w->fs[w->last_set].events; }
 // launched successor may have rebuilt the shared scheduling buffers (tile order, tile work, per-entry
 // work) for the flush after it, so a re-run neither reads nor writes them, and keygen's special-tile
 // flags may be the successor's too, so every tile is visited.
-EvCaps launch_pair_passes(gwaoi_world *w, FlushSet &S, DevFrame &Fn, DevFrame &P, uint64_t seq_base,
-                            const gw::SlotSp *s_ss_view, bool rerun = false, bool special_done = false) {
+EvCaps launch_pair_passes(gwaoi_world *w, FlushSet &S, DevFrame &Fn, DevFrame &P, const gw::FlushPlan &plan, bool rerun) {
     hipStream_t st = w->stream;
-    const uint32_t TBn = gw::combined_tiles(Fn.n), TBp = gw::combined_blocks(P.n);
-    const uint32_t half = TBn + TBp, entries = 2 * half;
-    gw::FrameView Vn = view_of(Fn), Vp = view_of(P);
+    const uint32_t half = gw::combined_tiles(Fn.n) + gw::combined_blocks(P.n), entries = 2 * half;
     // the pair passes write their streams into the scratch (capacity evtmp_cap), and k_finish copies
     // them into the set's buffer (ev_cap); a larger extent or count is an overflow (re-run)
     const EvCaps caps{S.evtmp_cap, S.ev_cap};
-    const uint64_t cap = caps.tmp;
     // timed with the launch's own start/end events (no marker packets)
     const bool tc = w->timing_mask >> ST_COMBINED & 1u;
     if (tc) S.ev_used[ST_COMBINED] = true;
     const bool order = !rerun;
-    gw::launch_combined(Vn, S.cand, S.orec, seq_base, S.sc, S.evtmp, cap, S.tile_total, S.tile_base, half,
-                        order ? w->tile_order : nullptr, order ? w->tile_work : nullptr, rerun ? nullptr : w->ework,
-                        st,
+    gw::launch_combined(view_of(Fn), S.cand, S.orec, plan.seq_base, S.sc, S.evtmp, caps.tmp, S.tile_total, S.tile_base,
+                        half, order ? w->tile_order : nullptr, order ? w->tile_work : nullptr, rerun ? nullptr : w->ework, st,
                         tc ? S.ev[ST_COMBINED][0] : nullptr, tc ? S.ev[ST_COMBINED][1] : nullptr);
-    if (!special_done) {  // (special_done: it ran in the sort's arrival launch)
+    if (rerun || !plan.sp_fused) {  // (else it ran in the sort's arrival launch)
+        gw::SpecialJob J = special_job(w, S, P, Fn, plan);
+        if (rerun) J.special = nullptr;
         stage_begin(w, S, ST_SPECIAL);
-        gw::launch_pairs(Vp, S.srec, s_ss_view, seq_base, S.sc, S.evtmp, cap, S.tile_total, S.tile_base, TBn,
-                         half, rerun ? nullptr : w->special, st);
+        gw::launch_pairs(J, st);
         stage_end(w, S, ST_SPECIAL);
     }
     // tile order + TickOut + the per-space bboxes for the next flush's grid (one launch)
@@ -839,148 +855,157 @@ int poison(gwaoi_world *w, int rc) {
     return rc;
 }
 
-void replay_deferred(gwaoi_world *w);
+// What the plan is made from (all but gen_same: tick_launch reads it after flush_ensure).
+gw::FlushFacts flush_facts(gwaoi_world *w, const DevFrame &P, const DevFrame &Fn, uint32_t total_cells) {
+    gw::FlushFacts f{};
+    f.n_prev = P.n; f.n_app_host = (uint32_t)w->new_slots.size(); f.dev_app = w->dev_app; f.n_alive = w->n_alive;
+    f.n_ops = (uint32_t)w->n_ops; f.n_runs = w->runs.size(); f.max_slots = w->max_slots;
+    f.tiles_new = gw::combined_tiles(f.n_alive); f.tiles_prev = gw::combined_blocks(f.n_prev);
+    f.all_plain_moves = true;
+    for (const Run &r : w->runs) {
+        if (!r.device) f.host_ops += r.hend - r.hbegin;
+        if (!r.device || r.kind != RUN_MOVE || r.dseq || r.dsp) f.all_plain_moves = false;
+    }
+    f.dev_struct = w->dev_struct; f.unique_moves = w->unique_moves; f.have_bucketed = w->mv_binned != nullptr;
+    f.force_radix = w->force_radix; f.force_copy = w->force_copy; f.check_stages = w->check_stages;
+    f.timing_mask = w->timing_mask; f.ovl_ok = w->ovl_ok; f.mid_last = w->mid_last;
+    const uint32_t ns = std::max(1u, w->n_space_ids);
+    auto cut_with = [&](const DevFrame &fr) {
+        return fr.hgrid.size() == ns && !std::memcmp(fr.hgrid.data(), w->h_grid, ns * sizeof(SpaceGrid));
+    };
+    f.total_cells = total_cells;
+    f.prev_grid_same = P.total_cells == total_cells && cut_with(P);
+    f.frame_grid_same = cut_with(Fn);
+    f.sort_tiles = gw::incr_sort_tiles(total_cells);
+    f.parts_max = gw::gather_parts(w->max_slots); f.parts_new = gw::gather_parts(f.n_alive);
+    f.cur = w->cur; f.launch_set = w->launch_set; f.seq_floor = w->seq_floor;
+    return f;
+}
 
-// The flush, first half: close the op queue and launch the whole pipeline on
-// the world's stream, ending with the D2H of the flush's summary (TickOut);
-// returns without waiting.  Calls made until tick_finish are deferred (see
-// Deferred).  A failure before any kernel was queued returns with nothing in
-// flight.
-int tick_launch(gwaoi_world *w) {
-    hipStream_t st = w->stream;
+// Room for the flush (a buffer that grows waits for the stream and counts as an enqueue: gen).
+int flush_ensure(gwaoi_world *w, FlushSet &S, DevFrame &Fn, const gw::FlushFacts &f, uint32_t total_rows) {
     int rc;
-    const uint32_t tick_id = ++w->tick_id;
-    const uint64_t seq_base = w->seq_floor;  // every seq of this flush is >= seq_base > every earlier one
-    const uint32_t n_ops = (uint32_t)w->n_ops;
-
-    // the previous flush's frame, and one no flush that may still be re-run reads
-    const int p_idx = w->cur, n_idx = (w->cur + 1) % 3;
-    DevFrame &P = w->fr[p_idx];   // previous flush
-    DevFrame &Fn = w->fr[n_idx];  // this flush
-    const int set = w->launch_set;
-    FlushSet &S = w->fs[set];
-    const uint32_t n_prev = P.n;
-    const uint32_t n_app_host = (uint32_t)w->new_slots.size();
-    const uint32_t n_app = n_app_host + w->dev_app;
-    const uint32_t n_total = n_prev + n_app;
-    const uint32_t n_new = w->n_alive;
-
-    (void)hipGetLastError();  // the launch check below must see this flush's launches only
-    // a copy-out still reading a flush set's events (gwaoi_tick_finish) ends before this
-    // flush writes into a set
-    if (w->out_pending) HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->out_ev, 0));
-    // grid for this flush
-    uint32_t total_cells = 0, total_rows = 0;
-    choose_grids(w, total_cells, total_rows);
-    for (uint32_t s = 0; s < w->n_space_ids; ++s) w->spaces[s].pend = false;  // consumed by this grid
-    const size_t entries = 2 * ((size_t)gw::combined_tiles(n_new) + gw::combined_blocks(n_prev));
-    if ((rc = ensure_cells(w, Fn, total_cells))) return rc;
+    const size_t entries = gw::flush_entries(f);
+    if ((rc = ensure_cells(w, Fn, f.total_cells))) return rc;
     if ((rc = ensure_tile_entries(w, S, entries))) return rc;
     // a set whose twin grew on an overflow grows alike before its next flush (one re-run, not two)
-    if (S.ev_cap < w->fs[set ^ 1].ev_cap && (rc = ensure_events(w, S, w->fs[set ^ 1].ev_cap, 0, true))) return rc;
-    size_t host_ops = 0;
-    for (const Run &r : w->runs)
-        if (!r.device) host_ops += r.hend - r.hbegin;
-    if ((rc = ensure_ops(w, host_ops))) return rc;
-    const size_t scan_need = std::max<size_t>({gw::radix_hist_elems(std::max(n_total, 1u)), (size_t)total_cells + 1,
-                                               (size_t)total_rows + 1, entries + 1});
+    const uint64_t twin_cap = w->fs[f.launch_set ^ 1].ev_cap;
+    if (S.ev_cap < twin_cap && (rc = ensure_events(w, S, twin_cap, 0, true))) return rc;
+    if ((rc = ensure_ops(w, f.host_ops))) return rc;
+    const size_t scan_need = std::max<size_t>({gw::radix_hist_elems(std::max(gw::flush_n_total(f), 1u)),
+                                               (size_t)f.total_cells + 1, (size_t)total_rows + 1, entries + 1});
     if ((rc = ensure_scan_tmp(w, scan_need))) return rc;
-    Fn.total_cells = total_cells;
-    Fn.n = n_new;
+    Fn.total_cells = f.total_cells;
+    Fn.n = f.n_alive;
+    if (gw::flush_incr(f) && (rc = ensure_incr(w, f.total_cells))) return rc;
+    return GWAOI_OK;
+}
 
-    const uint32_t ns = std::max(1u, w->n_space_ids);
-    const bool grid_same = Fn.hgrid.size() == ns && !std::memcmp(Fn.hgrid.data(), w->h_grid, ns * sizeof(SpaceGrid));
-    // the previous frame was cut with the same grid: its cells and keys are this flush's
-    const bool incr = !w->force_radix && n_prev > 0 && P.total_cells == total_cells && P.hgrid.size() == ns &&
-                      !std::memcmp(P.hgrid.data(), w->h_grid, ns * sizeof(SpaceGrid));
-    if (incr && (rc = ensure_incr(w, total_cells))) return rc;
-    // Overlap (speculative launches): this flush's early kernels (apply .. gather) go on the early
-    // stream behind the previous flush's early kernels (its set's mid_ev), while that flush's pair
-    // passes and finish still run on the stream; this flush's pair passes wait for its own early
-    // kernels.  Nothing the early kernels touch is read or written by the previous flush's pair
-    // passes or finish: the scratch, tile totals and boxes are per set, the frames rotate over three,
-    // and the special pass rides on the arrival launch (it reads the previous frame early).  Only when
-    // nothing else was queued on the stream since the previous flush's launch (gen), and with no
-    // stage timing but the combined pass's.
-#ifdef GWAOI_EXP_NO_OVERLAP  // diagnostics build only: one flush at a time (the A/B of the overlap)
-    const bool ovl = false;
-#else
-    const bool ovl = w->ovl_ok && w->mid_last && w->gen == w->gen_launch && incr && n_prev > 0 &&
-                     (w->timing_mask & ~(1u << ST_COMBINED)) == 0 && !w->check_stages;
-#endif
-    if (ovl) {
-        st = w->early_st;
-        HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->fs[set ^ 1].mid_ev, 0));
+// The stream of the early kernels, and what they wait for.  Overlap (plan.ovl, speculative launches):
+// this flush's early kernels (apply .. gather) go on the early stream behind the previous flush's
+// early kernels (its set's mid_ev), while that flush's pair passes and finish still run on the
+// stream; this flush's pair passes wait for its own early kernels.  Nothing the early kernels touch
+// is read or written by the previous flush's pair passes or finish: the scratch, tile totals and
+// boxes are per set, the frames rotate over three, and the special pass rides on the arrival launch
+// (it reads the previous frame early).
+int flush_open(gwaoi_world *w, DevFrame &Fn, const gw::FlushPlan &plan, hipStream_t *st) {
+    if (plan.ovl) {
+        *st = w->early_st;
+        HIP_TRY(w->last_error, hipStreamWaitEvent(*st, w->fs[plan.set ^ 1].mid_ev, 0));
         w->dbg.overlapped_flushes++;
     }
-    if (!grid_same) {
-        HIP_TRY(w->last_error, hipMemcpyAsync(Fn.grid, w->h_grid, sizeof(SpaceGrid) * ns, hipMemcpyHostToDevice, st));
+    if (!plan.grid_same) {
+        const uint32_t ns = std::max(1u, w->n_space_ids);
+        HIP_TRY(w->last_error, hipMemcpyAsync(Fn.grid, w->h_grid, sizeof(SpaceGrid) * ns, hipMemcpyHostToDevice, *st));
         Fn.hgrid.assign(w->h_grid.get(), w->h_grid + ns);
     }
     // the staged move batches' H2D copies (copy stream) land before the flush reads them
     if (w->copy_pending) {
-        HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->copy_ev, 0));
+        HIP_TRY(w->last_error, hipStreamWaitEvent(*st, w->copy_ev, 0));
         w->copy_pending = false;
     }
-    // device runs only (device Enter/Leave batches included: their ops carry the space, the appended
-    // entries are initialised first and S' is copied, so the single-pass apply handles them)
-    const bool moves_only = n_ops && host_ops == 0 && w->runs.size() <= gw::MAX_MOVE_RUNS && n_ops <= w->max_slots;
-    // Virtual S': a flush of Moved batches only (or of nothing) changes no space and appends
-    // no entry, so S' needs no copy of the previous frame: its spaces ARE the previous frame's,
-    // and the records no op wrote are taken from the previous frame by k_keygen (seq check).
-    const bool virt = n_app == 0 && host_ops == 0 && !w->dev_struct && (moves_only || n_ops == 0) && !w->force_copy;
-    const gw::SlotSp *s_ss_view = virt ? P.ss : S.sss;
-    gw::MoveRuns RS{};
-    if (moves_only) {
+    return GWAOI_OK;
+}
+
+// Op j0 .. of the flush as the single-pass apply takes a device run.
+gw::MoveRun move_run(const Run &r, uint32_t j0) {
+    gw::MoveRun m{};
+    m.ds = r.ds; m.dx = r.dx; m.dz = r.dz; m.dseq = r.dseq; m.dsp = r.dsp; m.seq0 = r.seq0;
+    m.sp_def = r.kind == RUN_MOVE ? gw::SP_KEEP : r.kind == RUN_ENTER ? r.space : gw::SP_DEAD;
+    m.j0 = j0; m.n = (uint32_t)r.dn;
+    return m;
+}
+
+// Counters, tile totals, bbox fold identity; S' <- the previous frame unless virtual; the first
+// Moved run's claims.  Not incremental: cell_start zeroed for the cell count (the incremental sort
+// writes it, and leaves its own cell counts zero).  A unique-moves flush on the previous grid has no
+// prologue: keygen does the zeroing (flush_keys_sort).
+void flush_prologue(gwaoi_world *w, FlushSet &S, DevFrame &P, DevFrame &Fn, const gw::FlushPlan &plan, hipStream_t st) {
+    if (plan.uniq) w->dbg.unique_flushes++;
+    if (plan.skip_prologue) return;
+    gw::MoveRun run0{};
+    if (plan.mark_run0) run0 = move_run(w->runs[0], 0);
+    gw::launch_prologue(S.sc, Fn.cell_start, plan.incr ? 0 : (size_t)Fn.total_cells + 1, S.tile_total,
+                        gw::tile_total_elems(plan.entries), dev_bbox(S), w->n_space_ids, plan.n_copy, P.rec, P.ss,
+                        S.srec, S.sss, plan.mark_run0 ? &run0 : nullptr, w->max_slots, w->sinfo, w->tick_id,
+                        plan.n_unique, st);
+}
+
+// A queue with host ops: host runs -> device op buffers (device runs are read in place), then every
+// run's claims, then every run's apply.
+int apply_host_ops(gwaoi_world *w, FlushSet &S, const gw::FlushPlan &plan, hipStream_t st) {
+    size_t hat = 0;
+    for (const Run &r : w->runs) {
+        if (r.device) continue;
+        const size_t k = r.hend - r.hbegin;
+        HIP_TRY(w->last_error, hipMemcpyAsync(w->op_slot + hat, w->h_op_slot.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(w->last_error, hipMemcpyAsync(w->op_x + hat, w->h_op_x.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(w->last_error, hipMemcpyAsync(w->op_z + hat, w->h_op_z.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(w->last_error, hipMemcpyAsync(w->op_sp + hat, w->h_op_sp.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(w->last_error, hipMemcpyAsync(w->op_seq + hat, w->h_op_seq.data() + r.hbegin, k * 8, hipMemcpyHostToDevice, st));
+        hat += k;
+    }
+    for (int pass = 0; pass < 2; ++pass) {
         uint32_t j0 = 0;
+        size_t hoff = 0;
         for (const Run &r : w->runs) {
-            gw::MoveRun &m = RS.r[RS.count++];
-            m.ds = r.ds; m.dx = r.dx; m.dz = r.dz; m.dseq = r.dseq; m.dsp = r.dsp; m.seq0 = r.seq0;
-            m.sp_def = r.kind == RUN_MOVE ? gw::SP_KEEP : r.kind == RUN_ENTER ? r.space : gw::SP_DEAD;
-            m.j0 = j0; m.n = (uint32_t)r.dn;
-            j0 += (uint32_t)r.dn;
+            const uint32_t *sl, *sps;
+            const float *xs, *zs;
+            const unsigned long long *sq;
+            uint64_t seq0 = 0;
+            uint32_t k;
+            const uint32_t sp_def = !r.device || r.kind == RUN_MOVE ? gw::SP_KEEP
+                                    : r.kind == RUN_ENTER ? r.space : gw::SP_DEAD;
+            if (r.device) {
+                sl = r.ds; xs = r.dx; zs = r.dz; sps = r.dsp; sq = r.dseq; seq0 = r.seq0; k = (uint32_t)r.dn;
+            } else {
+                k = (uint32_t)(r.hend - r.hbegin);
+                sl = w->op_slot + hoff; xs = w->op_x + hoff; zs = w->op_z + hoff; sps = w->op_sp + hoff;
+                sq = w->op_seq + hoff;
+                hoff += k;
+            }
+            if (pass == 0)
+                gw::launch_ops_claim(sl, k, j0, w->max_slots, w->sinfo, w->tick_id, S.sc, st);
+            else
+                gw::launch_ops_apply(sl, xs, zs, sps, sp_def, k, j0, w->max_slots, w->sinfo, w->tick_id, plan.n_total,
+                                     sq, seq0, plan.seq_base, r.device && r.dseq, S.srec, S.sss, S.sc, st);
+            j0 += k;
         }
     }
-    // counters, tile totals, bbox fold identity; S' <- the previous frame unless virtual; the
-    // first Moved run's claims
-    const bool bucketed = moves_only && w->mv_binned;
-    // GWAOI_F_UNIQUE_MOVES: plain device Moved batches (implicit seqs, the slot's own space) are
-    // applied without last-op claims; keygen's written-entry count checks the promise
-    bool uniq = w->unique_moves && moves_only && virt && !bucketed;
-    for (const Run &r : w->runs)
-        if (uniq && (!r.device || r.kind != RUN_MOVE || r.dseq || r.dsp)) uniq = false;
-    const gw::MoveRun *mark = moves_only && !bucketed && !uniq ? &RS.r[0] : nullptr;
-    if (uniq) w->dbg.unique_flushes++;
-    const uint32_t n_unique = uniq ? (uint32_t)n_ops : 0u;
-    const uint32_t n_copy = virt ? 0u : n_prev;
-    // a unique-moves flush on the previous grid has no prologue: its apply writes only
-    // sc->err_apply / ndrop (zero whenever a flush begins) and keygen does the zeroing (TickZero)
-    gw::TickZero tz{};
-    if (uniq && incr) {
-        tz.sc = S.sc;
-        tz.z1 = S.tile_total;
-        tz.n1 = (uint32_t)gw::tile_total_elems(entries);
-        tz.bbox = dev_bbox(S);
-        tz.n_spaces = w->n_space_ids;
-        tz.n_unique = n_unique;
-    } else if (incr)
-        gw::launch_prologue(S.sc, reinterpret_cast<uint32_t *>(w->cnt64.get()),
-                            gw::scan_rezeroes_counts() ? 0 : 2 * ((size_t)total_cells + 1), S.tile_total,
-                            gw::tile_total_elems(entries), dev_bbox(S), w->n_space_ids, n_copy, P.rec, P.ss, S.srec, S.sss, mark,
-                            w->max_slots, w->sinfo, tick_id, n_unique, st);
-    else
-        gw::launch_prologue(S.sc, Fn.cell_start, (size_t)total_cells + 1, S.tile_total, gw::tile_total_elems(entries), dev_bbox(S),
-                            w->n_space_ids, n_copy, P.rec, P.ss, S.srec, S.sss, mark, w->max_slots, w->sinfo,
-                            tick_id, n_unique, st);
+    return GWAOI_OK;
+}
 
-    // ---- apply queued ops onto S'
+// The queued ops onto S': the appended entries first (host Enters, then the device Enter batches in
+// queue order), then the ops through the bucketed, the single-pass or the claim + apply path.
+int flush_apply(gwaoi_world *w, FlushSet &S, DevFrame &P, const gw::FlushPlan &plan, hipStream_t st) {
+    const uint32_t n_prev = P.n, n_app_host = (uint32_t)w->new_slots.size();
     stage_begin(w, S, ST_APPLY);
     if (n_app_host) {
         HIP_TRY(w->last_error, hipMemcpyAsync(w->new_slots_d, w->new_slots.data(), n_app_host * sizeof(uint32_t),
                                hipMemcpyHostToDevice, st));
         gw::launch_init_appended(w->new_slots_d, n_app_host, n_prev, S.srec, S.sss, w->sinfo, w->max_slots, S.sc, st);
     }
-    if (w->dev_app) {  // device Enter batches: their slots are appended after the host ones, in queue order
+    if (w->dev_app) {
         uint32_t base = n_prev + n_app_host;
         for (const Run &r : w->runs)
             if (r.device && r.kind == RUN_ENTER) {
@@ -988,193 +1013,120 @@ int tick_launch(gwaoi_world *w) {
                 base += (uint32_t)r.dn;
             }
     }
-    if (bucketed) {  // the per-tick position sync: ops regrouped by slot bucket, last op per slot in LDS
-        gw::launch_moves_bucketed(RS, w->max_slots, w->sinfo, n_total, seq_base, S.srec, virt ? nullptr : S.sss,
-                                  S.sc, w->mv_hist, w->scan_tmp, w->mv_binned, st);
-    } else if (moves_only) {  // one pass + fixup of repeated slots (run 0's claims: the prologue)
+    gw::MoveRuns RS{};
+    if (plan.moves_only) {
+        uint32_t j0 = 0;
+        for (const Run &r : w->runs) {
+            RS.r[RS.count++] = move_run(r, j0);
+            j0 += (uint32_t)r.dn;
+        }
+    }
+    if (plan.bucketed) {  // the per-tick position sync: ops regrouped by slot bucket, last op per slot in LDS
+        gw::launch_moves_bucketed(RS, w->max_slots, w->sinfo, plan.n_total, plan.seq_base, S.srec,
+                                  plan.virt ? nullptr : S.sss.get(), S.sc, w->mv_hist, w->scan_tmp, w->mv_binned, st);
+    } else if (plan.moves_only) {  // one pass + fixup of repeated slots (run 0's claims: the prologue)
 #ifdef GWAOI_EXP_HOSTTIME
         if (w->ovl_ok)  // (speculative launches only: ht_entry is their gwaoi_tick_finish call's)
             w->ht[0] += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w->ht_entry).count();
 #endif
-        gw::launch_moves(RS, w->max_slots, w->sinfo, tick_id, n_total, seq_base, S.srec, virt ? nullptr : S.sss,
-                         P.rec, n_prev, S.sc, w->coll, 1u, uniq, st);
-    } else if (n_ops) {
-        // host runs -> device op buffers; device runs are read in place
-        size_t hat = 0;
-        for (const Run &r : w->runs) {
-            if (r.device) continue;
-            const size_t k = r.hend - r.hbegin;
-            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_slot + hat, w->h_op_slot.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_x + hat, w->h_op_x.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_z + hat, w->h_op_z.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_sp + hat, w->h_op_sp.data() + r.hbegin, k * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(w->last_error, hipMemcpyAsync(w->op_seq + hat, w->h_op_seq.data() + r.hbegin, k * 8, hipMemcpyHostToDevice, st));
-            hat += k;
-        }
-        for (int pass = 0; pass < 2; ++pass) {
-            uint32_t j0 = 0;
-            size_t hoff = 0;
-            for (const Run &r : w->runs) {
-                const uint32_t *sl;
-                const float *xs, *zs;
-                const uint32_t *sps;
-                const unsigned long long *sq;
-                uint64_t seq0 = 0;
-                uint32_t k;
-                const uint32_t sp_def = !r.device || r.kind == RUN_MOVE ? gw::SP_KEEP
-                                        : r.kind == RUN_ENTER ? r.space : gw::SP_DEAD;
-                if (r.device) {
-                    sl = r.ds; xs = r.dx; zs = r.dz; sps = r.dsp; sq = r.dseq; seq0 = r.seq0; k = (uint32_t)r.dn;
-                } else {
-                    k = (uint32_t)(r.hend - r.hbegin);
-                    sl = w->op_slot + hoff; xs = w->op_x + hoff; zs = w->op_z + hoff; sps = w->op_sp + hoff;
-                    sq = w->op_seq + hoff;
-                    hoff += k;
-                }
-                if (pass == 0)
-                    gw::launch_ops_claim(sl, k, j0, w->max_slots, w->sinfo, tick_id, S.sc, st);
-                else
-                    gw::launch_ops_apply(sl, xs, zs, sps, sp_def, k, j0, w->max_slots, w->sinfo, tick_id, n_total, sq, seq0,
-                                         seq_base, r.device && r.dseq, S.srec, S.sss, S.sc, st);
-                j0 += k;
-            }
-        }
+        gw::launch_moves(RS, w->max_slots, w->sinfo, w->tick_id, plan.n_total, plan.seq_base, S.srec,
+                         plan.virt ? nullptr : S.sss.get(), P.rec, n_prev, S.sc, w->coll, 1u, plan.uniq, st);
+    } else if (w->n_ops) {
+        if (int rc = apply_host_ops(w, S, plan, st)) return rc;
     }
     stage_end(w, S, ST_APPLY);
+    return GWAOI_OK;
+}
 
-    // ---- keys (+ d_rel, bmax) and stable sort
+// Keys (+ d_rel, bmax) and the stable sort: incremental on the previous frame's cells, with the
+// special pass and the gather riding on its launches where the plan says so, else the radix sort.
+// Returns which of the world's key / value buffers holds the radix sort's result.
+int flush_keys_sort(gwaoi_world *w, FlushSet &S, DevFrame &P, DevFrame &Fn, const gw::FlushPlan &plan, hipStream_t st) {
+    const uint32_t total_cells = Fn.total_cells, n_prev = P.n;
+    gw::TickZero tz{};  // the flush had no prologue: keygen zeroes
+    if (plan.skip_prologue)
+        tz = gw::TickZero{S.sc, S.tile_total, (uint32_t)gw::tile_total_elems(plan.entries), dev_bbox(S),
+                          w->n_space_ids, plan.n_unique};
     stage_begin(w, S, ST_KEYGEN);
-    gw::launch_keygen(S.srec, s_ss_view, n_total, Fn.grid, total_cells, w->keys[0], w->vals[0], P.rec, P.ss, P.grid,
-                      n_prev, w->blk, S.sc, P.key, incr ? w->cnt64 : nullptr, seq_base, w->special, tz,
-                      incr ? w->scan64_tmp : nullptr, st);
+    gw::launch_keygen(S.srec, s_ss_view(S, P, plan), plan.n_total, Fn.grid, total_cells, w->keys[0], w->vals[0], P.rec,
+                      P.ss, P.grid, n_prev, w->blk, S.sc, P.key, plan.incr ? w->cnt64.get() : nullptr, plan.seq_base,
+                      w->special, tz, plan.incr ? w->scan64_tmp.get() : nullptr, st);
     stage_end(w, S, ST_KEYGEN);
     stage_begin(w, S, ST_SORT);
     int which = 1;
-    // the special pass rides on the sort's arrival launch (k_arrive_special) unless it is timed;
-    // launch_pair_passes then skips its own launch
-    const bool sp_fused = incr && !(w->timing_mask >> ST_SPECIAL & 1u) && n_prev > 0;
-    gw::SpecialJob spj{};
-    if (sp_fused) {
-        const uint32_t TBn = gw::combined_tiles(n_new), TBp = gw::combined_blocks(n_prev);
-        spj.F = view_of(P);
-        spj.O_rec = S.srec;
-        spj.O_ss = s_ss_view;
-        spj.seq_base = seq_base;
-        spj.sc = S.sc;
-        spj.tmp = reinterpret_cast<uint2 *>(S.evtmp.get());
-        spj.cap = S.evtmp_cap;
-        spj.tile_total = S.tile_total;
-        spj.tile_base = S.tile_base;
-        spj.tile_off = TBn;
-        spj.leave_off = TBn + TBp;
-        spj.special = w->special;
-        spj.n_tiles = TBp;
-    }
-    // the gather rides on the incremental sort's merge launch (k_merge_gather, one bbox part per
-    // scan tile) unless it is timed or the grid has more scan tiles than the set has parts
-#ifdef GWAOI_EXP_UNFUSED_GATHER  // diagnostics build only: the two launches
-    const bool ga_fused = false;
-#else
-    const bool ga_fused = incr && !(w->timing_mask >> ST_GATHER & 1u) &&
-                          gw::incr_sort_tiles(total_cells) <= gw::gather_parts(w->max_slots);
-#endif
-    S.n_parts = ga_fused ? gw::incr_sort_tiles(total_cells) : gw::gather_parts(n_new);
-    gw::GatherJob gj{};
-    if (ga_fused) {
-        gj.n_new = n_new;
-        gj.n_prev = n_prev;
-        gj.s_rec = S.srec;
-        gj.s_ss = s_ss_view;
-        gj.p_rec = P.rec;
-        gj.p_ss = P.ss;
-        gj.f_rec = Fn.rec;
-        gj.f_ss = Fn.ss;
-        gj.o_rec = S.orec;
-        gj.cand = S.cand;
-        gj.grid = Fn.grid;
-        gj.info = w->sinfo;
-        gj.sc = S.sc;
-        gj.bbox = dev_bbox(S);
-        gj.n_spaces = w->n_space_ids;
-        gj.parts = S.bbox_parts;
-    }
-    if (incr) {
+    S.n_parts = plan.n_parts;
+    if (plan.incr) {
+        gw::SpecialJob spj{};
+        if (plan.sp_fused) spj = special_job(w, S, P, Fn, plan);
+        gw::GatherJob gj{};
+        if (plan.ga_fused) gj = gather_job(w, S, P, Fn, plan);
         w->dbg.incremental_sorts++;
-        gw::incremental_sort(w->keys[0], n_total, n_prev, P.key, P.cell_start, w->cnt64, total_cells,
+        gw::incremental_sort(w->keys[0], plan.n_total, n_prev, P.key, P.cell_start, w->cnt64, total_cells,
                              total_cells, Fn.cell_start, w->arr_pos, w->arr_idx, w->scan64_tmp, w->vals[1],
-                             Fn.key, w->blk, S.sc, sp_fused ? &spj : nullptr, ga_fused ? &gj : nullptr,
+                             Fn.key, w->blk, S.sc, plan.sp_fused ? &spj : nullptr, plan.ga_fused ? &gj : nullptr,
                              st);  // the sorted keys ARE the frame's
     } else {
-        gw::SortBuffers sb;
-        sb.keys[0] = w->keys[0];
-        sb.keys[1] = w->keys[1];
-        sb.vals[0] = w->vals[0];
-        sb.vals[1] = w->vals[1];
-        sb.hist = w->hist;
-        sb.scan_tmp = w->scan_tmp;
-        which = gw::radix_sort(sb, n_total, bitlen(total_cells), st);
+        gw::SortBuffers sb{{w->keys[0], w->keys[1]}, {w->vals[0], w->vals[1]}, w->hist, w->scan_tmp};
+        which = gw::radix_sort(sb, plan.n_total, bitlen(total_cells), st);
     }
     stage_end(w, S, ST_SORT);
-    const uint32_t *skeys = incr ? Fn.key : w->keys[which];
-    const uint32_t *perm = w->vals[which];
+    return which;
+}
 
-    // ---- new frame + previous state in the new order
-    if (!ga_fused) {
+// The new frame + the previous state in the new order (unless the sort's merge launch gathered),
+// and cell_start = exclusive scan of entities per cell (zeroed by the prologue; the incremental
+// sort has written it already).
+void flush_gather_cells(gwaoi_world *w, FlushSet &S, DevFrame &P, DevFrame &Fn, const gw::FlushPlan &plan, int which,
+                        hipStream_t st) {
+    const uint32_t *skeys = plan.incr ? Fn.key : w->keys[which];
+    if (!plan.ga_fused) {
         stage_begin(w, S, ST_GATHER);
-        gw::launch_gather(perm, n_new, n_prev, S.srec, s_ss_view, P.rec, P.ss, Fn.rec, Fn.ss, S.orec, S.cand,
-                          Fn.grid, seq_base, w->sinfo, skeys, total_cells, n_total, S.sc, incr ? nullptr : Fn.key,
-                          dev_bbox(S), w->n_space_ids, S.bbox_parts, st);
+        gw::launch_gather(gather_job(w, S, P, Fn, plan), w->vals[which], skeys, Fn.total_cells, plan.n_total,
+                          plan.incr ? nullptr : Fn.key.get(), plan.seq_base, st);
         stage_end(w, S, ST_GATHER);
     }
-
-    // ---- cell_start = exclusive scan of entities per cell (zeroed by the prologue;
-    // the incremental sort has written it already)
-    if (!incr) {
+    if (!plan.incr) {
         stage_begin(w, S, ST_CELLS);
-        gw::launch_cell_count(skeys, n_new, Fn.cell_start, st);
-        gw::scan_exclusive(Fn.cell_start, Fn.cell_start, (size_t)total_cells + 1, w->scan_tmp, st);
+        gw::launch_cell_count(skeys, plan.n_new, Fn.cell_start, st);
+        gw::scan_exclusive(Fn.cell_start, Fn.cell_start, (size_t)Fn.total_cells + 1, w->scan_tmp, st);
         stage_end(w, S, ST_CELLS);
     }
+}
 
-    // the early kernels' end: the next (speculative) flush's early stream starts behind it, and an
-    // overlapped flush's pair passes wait for it on the stream
+// The early kernels' end: the next (speculative) flush's early stream starts behind it, and an
+// overlapped flush's pair passes wait for it on the stream.
+int flush_mid(gwaoi_world *w, FlushSet &S, const gw::FlushPlan &plan, hipStream_t st) {
     w->mid_last = false;
-    if (w->ovl_ok || ovl) {
+    if (w->ovl_ok || plan.ovl) {
         if (hipEventRecord(S.mid_ev, st) != hipSuccess ||
-            (ovl && hipStreamWaitEvent(w->stream, S.mid_ev, 0) != hipSuccess)) {
+            (plan.ovl && hipStreamWaitEvent(w->stream, S.mid_ev, 0) != hipSuccess)) {
             w->last_error = "flush mid event failed";
             return poison(w, GWAOI_EDEVICE);
         }
         w->mid_last = true;
     }
-    st = w->stream;
+    return GWAOI_OK;
+}
 
-    // ---- pair passes: combined over the new grid, special entities over the previous one
-    const EvCaps ev_cap = launch_pair_passes(w, S, Fn, P, seq_base, s_ss_view, false, sp_fused);
-
+// The flush is queued: check its launches, mark its end, close the op queue and keep what the
+// commit needs of it.
+int record_flight(gwaoi_world *w, FlushSet &S, const gw::FlushPlan &plan, EvCaps caps) {
     // from here on the device has rewritten SlotInfo for the new frame: any failure before the
-    // commit below leaves the world inconsistent (poisoned)
+    // commit leaves the world inconsistent (poisoned)
     if (hipGetLastError() != hipSuccess) {
         w->last_error = "kernel launch failed";
         return poison(w, GWAOI_EDEVICE);
     }
     // (k_finish writes the summary straight into pinned host memory: no copy)
-    if (hipEventRecord(S.done_ev, st) != hipSuccess) {
+    if (hipEventRecord(S.done_ev, w->stream) != hipSuccess) {
         w->last_error = "flush done event failed";
         return poison(w, GWAOI_EDEVICE);
     }
-    // the queue is closed: what the commit needs of it
     w->in_flight = true;
-    w->fl.tick_id = tick_id;
-    w->fl.entries = entries;
+    w->fl.plan = plan;
     w->fl.seq_next = w->seq_next;
-    w->fl.seq_base = seq_base;
     w->fl.dev_seq = w->dev_seq_pending;
-    w->fl.set = set;
-    w->fl.p_idx = p_idx;
-    w->fl.n_idx = n_idx;
-    w->fl.s_ss_view = s_ss_view;
-    w->fl.cap = ev_cap;
+    w->fl.cap = caps;
     w->launch_set ^= 1;
     w->fl.touched_alive.resize(w->touched.size());
     for (size_t i = 0; i < w->touched.size(); ++i) w->fl.touched_alive[i] = w->alive[w->touched[i]];
@@ -1183,6 +1135,45 @@ int tick_launch(gwaoi_world *w) {
     w->space_ops_queued = false;
     w->gen_launch = w->gen;
     return GWAOI_OK;
+}
+
+// The flush, first half: close the op queue and launch the whole pipeline on
+// the world's stream, ending with the flush's summary (TickOut) in pinned memory;
+// returns without waiting.  Calls made until tick_finish are deferred (see
+// Deferred).  A failure before any kernel was queued returns with nothing in
+// flight.
+int tick_launch(gwaoi_world *w) {
+    int rc;
+    ++w->tick_id;
+    // the previous flush's frame, and one no flush that may still be re-run reads (the plan's p_idx,
+    // n_idx and set)
+    DevFrame &P = w->fr[w->cur];
+    DevFrame &Fn = w->fr[(w->cur + 1) % 3];
+    FlushSet &S = w->fs[w->launch_set];
+    (void)hipGetLastError();  // the launch check below must see this flush's launches only
+    // a copy-out still reading a flush set's events (gwaoi_tick_finish) ends before this
+    // flush writes into a set
+    if (w->out_pending) HIP_TRY(w->last_error, hipStreamWaitEvent(w->stream, w->out_ev, 0));
+    // grid for this flush
+    uint32_t total_cells = 0, total_rows = 0;
+    choose_grids(w, total_cells, total_rows);
+    for (uint32_t s = 0; s < w->n_space_ids; ++s) w->spaces[s].pend = false;  // consumed by this grid
+
+    gw::FlushFacts facts = flush_facts(w, P, Fn, total_cells);
+    if ((rc = flush_ensure(w, S, Fn, facts, total_rows))) return rc;
+    facts.gen_same = w->gen == w->gen_launch;  // read last: a buffer that grew above was an enqueue
+    const gw::FlushPlan plan = gw::plan_flush(facts);
+
+    hipStream_t st = w->stream;
+    if ((rc = flush_open(w, Fn, plan, &st))) return rc;
+    flush_prologue(w, S, P, Fn, plan, st);
+    if ((rc = flush_apply(w, S, P, plan, st))) return rc;
+    const int which = flush_keys_sort(w, S, P, Fn, plan, st);
+    flush_gather_cells(w, S, P, Fn, plan, which, st);
+    if ((rc = flush_mid(w, S, plan, st))) return rc;
+    // pair passes: combined over the new grid, special entities over the previous one
+    const EvCaps caps = launch_pair_passes(w, S, Fn, P, plan, false);
+    return record_flight(w, S, plan, caps);
 }
 
 // Wait for a flush's summary: polls its event (a blocking wait adds tens of microseconds of wake-up).
@@ -1195,6 +1186,24 @@ int wait_done(gwaoi_world *w, hipEvent_t ev) {
 
 using Flight = decltype(gwaoi_world::fl);
 
+// The op queue of a flush that committed: its host op arrays and runs.
+void clear_op_queue(gwaoi_world *w) {
+    w->h_op_slot.clear();
+    w->h_op_x.clear();
+    w->h_op_z.clear();
+    w->h_op_sp.clear();
+    w->h_op_seq.clear();
+    w->runs.clear();
+    w->n_ops = 0;
+}
+
+// A flush's event count must fit the 32-bit counts of the C ABI.
+int check_event_count(gwaoi_world *w, const gw::TickOut &r) {
+    if (r.total64 <= 0xFFFFFFFFull) return GWAOI_OK;
+    w->last_error = "more than 2^32-1 events in one flush";
+    return poison(w, GWAOI_ECAPACITY);
+}
+
 // The host half of a flush's commit: its op queue becomes the world's state and
 // the calls deferred while it was in flight are queued for the next flush.  r:
 // the flush's summary (needed only after explicit-seq device batches; a
@@ -1204,97 +1213,24 @@ void commit_host(gwaoi_world *w, const gw::TickOut *r) {
     w->new_slots.clear();
     for (size_t i = 0; i < w->touched.size(); ++i) w->in_frame[w->touched[i]] = w->fl.touched_alive[i];
     w->touched.clear();
-    w->h_op_slot.clear();
-    w->h_op_x.clear();
-    w->h_op_z.clear();
-    w->h_op_sp.clear();
-    w->h_op_seq.clear();
-    w->runs.clear();
-    w->n_ops = 0;
+    clear_op_queue(w);
     if (w->dev_struct) w->slots_stale = true;
     w->dev_app = 0;
     w->dev_struct = false;
     if (r && w->fl.dev_seq && r->seq_max >= w->seq_next) w->seq_next = r->seq_max + 1;  // no call was made in flight
     w->dev_seq_pending = false;
     w->seq_floor = w->fl.dev_seq ? w->seq_next : w->fl.seq_next;
-    w->cur = w->fl.n_idx;
+    w->cur = w->fl.plan.n_idx;
     w->in_flight = false;
     replay_deferred(w);
 }
 
-// The flush, second half, for flight f: wait for the summary, grow the event
-// buffer and re-run the pair passes if needed, commit.  host_done: the host half
-// was committed ahead (a speculative launch of the next flush followed it; that
-// flush writes the other FlushSet and the third frame, so f's pair-pass inputs
-// are intact for a re-run, which then runs after it on the stream).  On return
-// the events are in the set's buffer (last_events).  *committed: the new frame
-// became the world's state (the events are valid and must be delivered, even
-// when the returned status reports a problem the device found in the queued
-// ops).  A failure after the device kernels have rewritten the per-slot records
-// but before the commit poisons the world.
-int finish_flight(gwaoi_world *w, const Flight &f, bool host_done, bool *committed) {
-    *committed = false;
-    hipStream_t st = w->stream;
-    int rc;
-    FlushSet &S = w->fs[f.set];
-    DevFrame &P = w->fr[f.p_idx];
-    DevFrame &Fn = w->fr[f.n_idx];
-    if (wait_done(w, S.done_ev) != GWAOI_OK) {
-        w->last_error = "flush did not complete: " + w->last_error;
-        if (w->fault_stage)
-            w->last_error += std::string(" (first failed stage wait: ") + (w->fault_before ? "before " : "after ") +
-                             w->fault_stage + ")";
-        return poison(w, GWAOI_EDEVICE);
-    }
-
-    gw::TickOut r = *tick_out(S);
-    if (r.total64 > 0xFFFFFFFFull) {
-        w->last_error = "more than 2^32-1 events in one flush";
-        return poison(w, GWAOI_ECAPACITY);
-    }
-    // compared with the capacities the passes had at launch: a regrow by another flush since then
-    // (shared scratch, or the twin set's catch-up) does not make the clipped events complete.
-    // The scratch extent is not the event count: the pair passes deal their pairs to the event
-    // streams by the XCD each block lands on, so a re-run's extent may differ from the overflowed
-    // run's.  The first re-run is sized for the extent seen; a second one for the worst case (every
-    // pair in one stream), which cannot overflow.  The set's buffer is sized by the count.
-    EvCaps cap_used = f.cap;
-    for (int attempt = 0; r.total64 > cap_used.out || r.ext64 > cap_used.tmp; ++attempt) {  // grow, re-run
-        stage_collect(w, S);
-        if (w->inject_regrow_fail) {
-            w->last_error = "event buffer regrow failed (injected)";
-            return poison(w, GWAOI_ENOMEM);
-        }
-        if (attempt == 2) {
-            w->last_error = "pair passes re-run: the event extent exceeds its worst-case bound";
-            return poison(w, GWAOI_EDEVICE);
-        }
-        const uint64_t need = attempt == 0 ? r.ext64 : std::max<uint64_t>(r.ext64, gw::ev_worst_extent(r.total64));
-        if ((rc = ensure_events(w, S, r.total64, need))) return poison(w, rc);
-        (void)hipGetLastError();  // a failure of an unrelated earlier call is not this re-run's
-        w->gen++;
-        gw::launch_zero(S.tile_total, gw::tile_total_elems(f.entries), st);
-        gw::launch_zero(&S.sc.get()->shard[0][0], gw::EV_SHARDS * 32, st);  // event streams
-        gw::launch_zero(S.sc.get()->dbg, gw::DBG_N, st);
-        cap_used = launch_pair_passes(w, S, Fn, P, f.seq_base, f.s_ss_view, true);
-        if (cap_used.tmp < need || cap_used.out < r.total64) {
-            w->last_error = "pair passes re-run: event buffers did not grow";
-            return poison(w, GWAOI_EDEVICE);
-        }
-        w->dbg.event_regrows++;
-        if (hipGetLastError() != hipSuccess || wait_stream(w) != GWAOI_OK) {
-            w->last_error = "pair passes re-run failed: " + w->last_error;
-            return poison(w, GWAOI_EDEVICE);
-        }
-        r = *tick_out(S);
-        if (r.total64 > 0xFFFFFFFFull) {
-            w->last_error = "more than 2^32-1 events in one flush";
-            return poison(w, GWAOI_ECAPACITY);
-        }
-    }
-    stage_collect(w, S);
-
-    // ---- commit
+// The commit of flight f with summary r: counters, the cell size the event counts recommend, the
+// per-space boxes for the next grid, the host half unless host_done.  Returns the status of the
+// problems the device found in the queued ops.
+int commit_flight(gwaoi_world *w, const Flight &f, const gw::TickOut &r, bool host_done, bool *committed) {
+    FlushSet &S = w->fs[f.plan.set];
+    DevFrame &Fn = w->fr[f.plan.n_idx];
     w->dbg.flushes++;
     w->dbg.combined_replays += r.dbg[gw::DBG_COMBINED_REPLAY];
     w->dbg.combined_queue_drains += r.dbg[gw::DBG_COMBINED_DRAIN];
@@ -1312,7 +1248,7 @@ int finish_flight(gwaoi_world *w, const Flight &f, bool host_done, bool *committ
             w->cpd_streak = 0;
         }
     }
-    w->last_set = f.set;
+    w->last_set = f.plan.set;
     const int4 *bb = tick_bbox(S);
     for (uint32_t s = 0; s < w->n_space_ids; ++s) {
         SpaceHost &SH = w->spaces[s];
@@ -1354,6 +1290,74 @@ int finish_flight(gwaoi_world *w, const Flight &f, bool host_done, bool *committ
     note(gw::ERR_MOVE_DEAD | gw::ERR_BAD_SLOT, GWAOI_ESTATE, "device batch moved a slot that is not live (move dropped)");
     if (st_err != GWAOI_OK) w->last_error = msg;
     return st_err;
+}
+
+// The flush, second half, for flight f: wait for the summary, grow the event
+// buffer and re-run the pair passes if needed, commit.  host_done: the host half
+// was committed ahead (a speculative launch of the next flush followed it; that
+// flush writes the other FlushSet and the third frame, so f's pair-pass inputs
+// are intact for a re-run, which then runs after it on the stream).  On return
+// the events are in the set's buffer (last_events).  *committed: the new frame
+// became the world's state (the events are valid and must be delivered, even
+// when the returned status reports a problem the device found in the queued
+// ops).  A failure after the device kernels have rewritten the per-slot records
+// but before the commit poisons the world.
+int finish_flight(gwaoi_world *w, const Flight &f, bool host_done, bool *committed) {
+    *committed = false;
+    hipStream_t st = w->stream;
+    int rc;
+    FlushSet &S = w->fs[f.plan.set];
+    DevFrame &P = w->fr[f.plan.p_idx];
+    DevFrame &Fn = w->fr[f.plan.n_idx];
+    if (wait_done(w, S.done_ev) != GWAOI_OK) {
+        w->last_error = "flush did not complete: " + w->last_error;
+        if (w->fault_stage)
+            w->last_error += std::string(" (first failed stage wait: ") + (w->fault_before ? "before " : "after ") +
+                             w->fault_stage + ")";
+        return poison(w, GWAOI_EDEVICE);
+    }
+
+    gw::TickOut r = *tick_out(S);
+    if ((rc = check_event_count(w, r))) return rc;
+    // compared with the capacities the passes had at launch: a regrow by another flush since then
+    // (shared scratch, or the twin set's catch-up) does not make the clipped events complete.
+    // The scratch extent is not the event count: the pair passes deal their pairs to the event
+    // streams by the XCD each block lands on, so a re-run's extent may differ from the overflowed
+    // run's.  The first re-run is sized for the extent seen; a second one for the worst case (every
+    // pair in one stream), which cannot overflow.  The set's buffer is sized by the count.
+    EvCaps cap_used = f.cap;
+    for (int attempt = 0; r.total64 > cap_used.out || r.ext64 > cap_used.tmp; ++attempt) {  // grow, re-run
+        stage_collect(w, S);
+        if (w->inject_regrow_fail) {
+            w->last_error = "event buffer regrow failed (injected)";
+            return poison(w, GWAOI_ENOMEM);
+        }
+        if (attempt == 2) {
+            w->last_error = "pair passes re-run: the event extent exceeds its worst-case bound";
+            return poison(w, GWAOI_EDEVICE);
+        }
+        const uint64_t need = attempt == 0 ? r.ext64 : std::max<uint64_t>(r.ext64, gw::ev_worst_extent(r.total64));
+        if ((rc = ensure_events(w, S, r.total64, need))) return poison(w, rc);
+        (void)hipGetLastError();  // a failure of an unrelated earlier call is not this re-run's
+        w->gen++;
+        gw::launch_zero(S.tile_total, gw::tile_total_elems(f.plan.entries), st);
+        gw::launch_zero(&S.sc.get()->shard[0][0], gw::EV_SHARDS * 32, st);  // event streams
+        gw::launch_zero(S.sc.get()->dbg, gw::DBG_N, st);
+        cap_used = launch_pair_passes(w, S, Fn, P, f.plan, true);
+        if (cap_used.tmp < need || cap_used.out < r.total64) {
+            w->last_error = "pair passes re-run: event buffers did not grow";
+            return poison(w, GWAOI_EDEVICE);
+        }
+        w->dbg.event_regrows++;
+        if (hipGetLastError() != hipSuccess || wait_stream(w) != GWAOI_OK) {
+            w->last_error = "pair passes re-run failed: " + w->last_error;
+            return poison(w, GWAOI_EDEVICE);
+        }
+        r = *tick_out(S);
+        if ((rc = check_event_count(w, r))) return rc;
+    }
+    stage_collect(w, S);
+    return commit_flight(w, f, r, host_done, committed);
 }
 
 int tick_finish(gwaoi_world *w, bool *committed) { return finish_flight(w, w->fl, false, committed); }
@@ -1463,13 +1467,7 @@ int sparse_try(gwaoi_world *w) {
     w->rel_pairs += (int64_t)w->last_n_enter - (int64_t)w->last_n_leave;
     w->last_set = set;
     w->launch_set ^= 1;
-    w->h_op_slot.clear();
-    w->h_op_x.clear();
-    w->h_op_z.clear();
-    w->h_op_sp.clear();
-    w->h_op_seq.clear();
-    w->runs.clear();
-    w->n_ops = 0;
+    clear_op_queue(w);
     w->seq_floor = w->seq_next;
     w->ticks++;
     // the staged batch was read (the stream was waited for): its staging words are free again
@@ -1623,9 +1621,9 @@ int gwaoi_world_create(const gwaoi_config *cfg, gwaoi_world **out) {
         hipMemset(w->sinfo.lastop, 0, N * sizeof(unsigned long long)) != hipSuccess)
         return fail(GWAOI_EDEVICE);
     // the bucketed apply for worlds whose SlotInfo outgrows the MALL (GWAOI_F_TEST_BUCKETED forces it)
-    w->moves_bucketed = N > gw::MV_MIN_SLOTS || (cfg->flags & GWAOI_F_TEST_BUCKETED);
+    const bool moves_bucketed = N > gw::MV_MIN_SLOTS || (cfg->flags & GWAOI_F_TEST_BUCKETED);
     size_t mv_hist_n = 0;
-    if (w->moves_bucketed && gw::moves_buckets((uint32_t)N) <= gw::MV_NB_MAX) {
+    if (moves_bucketed && gw::moves_buckets((uint32_t)N) <= gw::MV_NB_MAX) {
         mv_hist_n = std::max(gw::moves_hist_elems((uint32_t)N, (uint32_t)N),
                              ((size_t)1 << 20) + 2 * (size_t)gw::moves_buckets((uint32_t)N) + 2);
         if ((rc = gw::alloc_all(err, w->mv_hist, mv_hist_n, w->mv_binned, N))) return fail(rc);
@@ -2238,7 +2236,7 @@ SyncState *&world_sync(gwaoi_world *w) { return w->sync; }
 void world_set_error(gwaoi_world *w, const char *msg) { w->last_error = msg; }
 
 void world_flush_events(gwaoi_world *w, const uint32_t **events, const uint32_t **dcount, uint64_t *cap) {
-    FlushSet &S = w->fs[w->in_flight ? w->fl.set : w->last_set];
+    FlushSet &S = w->fs[w->in_flight ? w->fl.plan.set : w->last_set];
     *events = S.events;
     *dcount = reinterpret_cast<const uint32_t *>(S.dev_out.get());
     *cap = w->in_flight ? w->fl.cap.out : S.ev_cap;  // events the set's buffer holds (clipped to it)
@@ -2298,7 +2296,7 @@ int end_begin(gwaoi_world *w, bool *committed_out) {
         if (lrc == GWAOI_OK) w->dbg.speculative_launches++;
 #ifdef GWAOI_EXP_HOSTTIME
         const auto h1 = std::chrono::steady_clock::now();
-        (void)wait_done(w, w->fs[f.set].done_ev);
+        (void)wait_done(w, w->fs[f.plan.set].done_ev);
         const auto h2 = std::chrono::steady_clock::now();
 #endif
         rc = finish_flight(w, f, true, &committed);

@@ -1240,6 +1240,60 @@ def test_speculative_regrows_with_growing_crowd_gpu():
             np.testing.assert_array_equal(A.neighbors(i), B.neighbors(i))
 
 
+def test_stage_timing_paths_keep_parity_gpu():
+    """The launches a flush makes only under stage timing: the special pass and the gather on their
+    own (untimed, they ride on the incremental sort's launches) and the speculative launch that
+    does not overlap.  One stream of six chained flushes (a device Moved batch each, 5 % of the
+    entities teleporting: every flush has enters, leaves and special tiles) through four worlds,
+    untimed / all stages / only the special pass / only the gather timed: the same events in all
+    four, and only the untimed world overlaps its flushes."""
+    torch = pytest.importorskip("torch")
+    n, ticks = 2000, 6  # 8 combined tiles, 8 previous-frame tiles
+    rng = np.random.default_rng(11)
+    L = np.float32(1500.0)  # ~35 neighbours each
+    x = rng.uniform(0, L, n).astype(np.float32)
+    z = rng.uniform(0, L, n).astype(np.float32)
+    slots = np.arange(n, dtype=np.uint32)
+    dev = []
+    px, pz = x.copy(), z.copy()
+    for t in range(ticks):
+        px = np.clip(px + rng.uniform(-3, 3, n).astype(np.float32), 0, L).astype(np.float32)
+        pz = np.clip(pz + rng.uniform(-3, 3, n).astype(np.float32), 0, L).astype(np.float32)
+        jump = rng.choice(n, n // 20, replace=False)
+        px[jump] = rng.uniform(0, L, jump.size).astype(np.float32)
+        pz[jump] = rng.uniform(0, L, jump.size).astype(np.float32)
+        order = rng.permutation(n)
+        dev.append([torch.from_numpy(a).to("cuda:0") for a in (order.astype(np.int32), px[order], pz[order])])
+    torch.cuda.synchronize()
+    runs = []
+    for stages in ([], None, ["special"], ["gather"]):
+        with World(n) as w:
+            w.set_stage_timing(stages)
+            s = w.space_create(D)
+            w.enter_batch(s, slots, x, z)
+            w.tick()
+            w.moved_batch_device(*(b.data_ptr() for b in dev[0]), n)
+            w.tick_begin()
+            events = []
+            for t in range(ticks):
+                if t + 1 < ticks:
+                    w.moved_batch_device(*(b.data_ptr() for b in dev[t + 1]), n)
+                    ne, nl = w.tick_end_begin_device()
+                else:
+                    ne, nl = w.tick_end_device()
+                ge, gl = _device_events(w, ne, nl)
+                events.append((pair_keys(ge), pair_keys(gl)))
+            runs.append((events, w.debug_counters()))
+    base, d0 = runs[0]
+    assert all(e.size and l.size for e, l in base)
+    assert d0["speculative_launches"] == ticks - 1 and d0["overlapped_flushes"] > 0, d0
+    for (events, d), name in zip(runs[1:], ("all stages", "special", "gather")):
+        for t in range(ticks):
+            np.testing.assert_array_equal(events[t][0], base[t][0], err_msg=f"{name} timed, flush {t}: enters")
+            np.testing.assert_array_equal(events[t][1], base[t][1], err_msg=f"{name} timed, flush {t}: leaves")
+        assert d["speculative_launches"] == ticks - 1 and d["overlapped_flushes"] == 0, (name, d)
+
+
 def test_cell_size_switch_keeps_parity_gpu(oracle_mod):
     """Automatic cell size (gwaoi_config.cells_per_dist = 0): a sparse uniform space
     switches the grids to D/2, a contracted one back to D/3 (two flushes recommending
