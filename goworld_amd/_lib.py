@@ -70,6 +70,7 @@ SYNC_EXPORTS = [
     "gwaoi_sync_from_clients", "gwaoi_sync_from_clients_device", "gwaoi_collect_sync_infos",
     "gwaoi_collect_sync_infos_device", "gwaoi_collect_client_events", "gwaoi_entity_enter_plain",
     "gwaoi_entity_leave_plain", "gwaoi_collect_broadcast", "gwaoi_collect_broadcast_device",
+    "gwaoi_collect_client_switch",
 ]
 
 # every function include/gwaoi_wire.h declares
@@ -234,6 +235,7 @@ def load():
         "gwaoi_collect_client_events": ([vp, P(GateRecords), P(GateRecords)], C.c_int),
         "gwaoi_collect_broadcast": ([vp, vp, vp, sz, P(GateRecords)], C.c_int),
         "gwaoi_collect_broadcast_device": ([vp, vp, vp, sz, P(GateRecords)], C.c_int),
+        "gwaoi_collect_client_switch": ([vp, vp, vp, vp, sz, P(GateRecords), P(GateRecords)], C.c_int),
         "gwaoi_wire_create": ([C.c_int, P(vp)], C.c_int),
         "gwaoi_wire_destroy": ([vp], None),
         "gwaoi_wire_last_error": ([vp], C.c_char_p),
@@ -687,6 +689,26 @@ class World:
         ids = [g.gate_ids[i] for i in range(g.n_gates)]
         off = [g.offsets[i] for i in range(g.n_gates + 1)] if g.n_gates else [0]
         return ids, off, g.records or 0
+
+    def collect_client_switch(self, slots, gates, clientids):
+        """Entity.SetClient for a batch (gwaoi_collect_client_switch): message m sets the client of
+        slots[m] to (gates[m], clientids[m]); clientids[m] is 16 bytes, or None for no client.
+        Returns ({gate_id: (n,48) create records}, {gate_id: (n,32) destroy records}) of the gates
+        that receive any, for the entities in each source's InterestedBy, and switches the clients."""
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.uint32).reshape(-1)
+        gt = np.ascontiguousarray(np.atleast_1d(gates), np.uint16).reshape(-1)
+        cl = list(clientids)
+        if gt.size != s.size or len(cl) != s.size:
+            raise ValueError(f"{s.size} slots but {gt.size} gates and {len(cl)} client ids")
+        ids = None
+        if any(c is not None for c in cl):
+            ids = _ids([bytes(16) if c is None else c for c in cl], s.size)
+        c, d = GateRecords(), GateRecords()
+        self._check(self._L.gwaoi_collect_client_switch(self._w, _p(s) if s.size else None, _p(gt) if s.size else None,
+                                                        _p(ids) if ids is not None else None, s.size,
+                                                        C.byref(c), C.byref(d)))
+        return ({k: a for k, a in _gate_dict(c, SYNC_OUT_REC).items() if len(a)},
+                {k: a for k, a in _gate_dict(d, DESTROY_REC).items() if len(a)})
 
 
 def _ids(ids, n) -> np.ndarray:

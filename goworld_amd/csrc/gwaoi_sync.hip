@@ -1,6 +1,6 @@
 // gwaoi_sync.hip -- entity position sync around the AOI path (include/gwaoi_sync.h).
 //
-// Four device passes, all on the world's stream:
+// Five device passes, all on the world's stream:
 //   decode    HandleSyncPositionYawFromClient (GameService.go:392-404): one
 //             lane per 32-B record, entity-id hash lookup, the record becomes
 //             op i of a device Moved batch (SLOT_NONE = skipped), Y/yaw by
@@ -16,6 +16,10 @@
 //             (Entity.go:743-917), source side: one wave per (source, flags)
 //             message; a record for the source's own client and one per B with
 //             rel(source, B) that has a client, grouped by gate.
+//   switch    Entity.SetClient / GiveClientTo (Entity.go:678-765), source side: one wave per
+//             (slot, new client) message; a destroy record for the old client and a create
+//             record for the new one per B with rel(source, B), grouped by gate; then the
+//             clients are switched.
 // Grouping by gate is a multisplit: a first pass counts records per
 // (gate, block) in LDS, an exclusive scan gives every (gate, block) its
 // base, a second pass writes each block's runs (the fan-out's first pass
@@ -848,7 +852,8 @@ __global__ __launch_bounds__(ST) void k_fan_write(FanArgs A) {
 // its waves every fourth one.  The source's window is walked twice and no hit list is kept:
 // k_cast_count counts the block's records per gate in LDS, the scan gives every (gate, block)
 // its base, k_cast_write repeats the walk (one body, cast_pass) and a hit takes the next
-// position of its gate's run from an LDS cursor.  The walk is k_fan_hits_wave's: lane j loads
+// position of its gate's run from an LDS cursor.  The walk (window_walk, shared with the client
+// switch) is k_fan_hits_wave's: lane j loads
 // row j's bounds, the rows are laid end to end and the wave reads 64 consecutive candidates
 // per step; only hits go on to the candidate's slot and the first 16 B of its slot record
 // (the gate), the other lanes re-read the source's (clamped index: no load under a per-lane
@@ -875,11 +880,78 @@ struct CastArgs {
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
+// One wave walks the go-aoi window of the source at frame index r0 (record R, slot-space S0):
+// exactly fan_window's cells (the same float32 margin, in the source's own space grid), lane j
+// loads row j's bounds, the rows are laid end to end and the wave reads 64 consecutive
+// candidates per step, CAST_WU steps with their loads in flight together.  After each group of
+// steps step(b, q, hit) runs with every lane active: lane ln's candidate of step u is frame
+// index b[u] with frame record q[u]; hit[u] is rel(source, candidate), never the source itself;
+// a lane past the window's end has b[u] == r0 and no hit.  Shared by the broadcast and the
+// client switch (wave w of the block, lane ln).
+template <class Step>
+__device__ __forceinline__ void window_walk(const FrameView &F, uint32_t r0, const Rec16 &R, const SlotSp &S0,
+                                            uint32_t w, uint32_t ln, Step &&step) {
+    __shared__ uint32_t s_adj[ST / 64][64];             // candidate index - position, per non-empty row
+    __shared__ uint32_t s_mark[ST / 64][CAST_WU * 64];  // a non-empty row starts at this position
+    const uint32_t *cs = F.cell_start;
+    const uint4 *frec = reinterpret_cast<const uint4 *>(F.rec);
+    const unsigned long long lt = (1ull << ln) - 1ull;
+    const unsigned long long le = ln == 63 ? ~0ull : (2ull << ln) - 1ull;
+    const SpaceGrid gr = F.grid[rfl(S0.sp)];
+    const float D = gr.D;
+    const float mx = (fabsf(R.x) + 3.0f * D) * 0x1p-20f, mz = (fabsf(R.z) + 3.0f * D) * 0x1p-20f;
+    const int cx0 = cell_of(R.x - D - mx, gr.ox, gr.inv, gr.gx), cx1 = cell_of(R.x + D + mx, gr.ox, gr.inv, gr.gx);
+    const int cz0 = cell_of(R.z - D - mz, gr.oz, gr.inv, gr.gz), cz1 = cell_of(R.z + D + mz, gr.oz, gr.inv, gr.gz);
+    const uint32_t span = rfl((uint32_t)(cx1 - cx0) + 1u), nrows = rfl((uint32_t)(cz1 - cz0) + 1u);
+    const uint32_t row0 = rfl(gr.base + (uint32_t)cz0 * gr.gx + (uint32_t)cx0), gx = rfl(gr.gx);
+    for (uint32_t j0 = 0; j0 < nrows; j0 += 64u) {
+        // lane t: row j0 + t of the window, its candidates [jb, je)
+        const uint32_t t = j0 + ln;
+        const uint32_t rb = row0 + min(t, nrows - 1u) * gx;
+        const uint32_t jb = cs[rb], je = cs[rb + span];
+        const uint32_t len = t < nrows ? je - jb : 0u;
+        const uint32_t incl = wave_scan_add(len);
+        const uint32_t ex = incl - len, T = rdl(incl, 63);
+        const unsigned long long nem = __ballot(len != 0u);
+        if (len) s_adj[w][__popcll(nem & lt)] = jb - ex;
+        for (uint32_t p0 = 0; p0 < T; p0 += CAST_WU * 64u) {
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) s_mark[w][u * 64 + ln] = 0u;
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            if (len && ex >= p0 && ex - p0 < CAST_WU * 64u) s_mark[w][ex - p0] = 1u;
+            uint32_t nr = (uint32_t)__popcll(__ballot(len != 0u && ex < p0));  // non-empty rows started before this step
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            uint32_t b[CAST_WU];
+            uint4 q[CAST_WU];
+            bool hit[CAST_WU];
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) {
+                const unsigned long long mk = __ballot(s_mark[w][u * 64 + ln] != 0u);
+                const uint32_t p = p0 + (uint32_t)u * 64u + ln;
+                const uint32_t row = nr + (uint32_t)__popcll(mk & le);  // rows started at or before p
+                nr += (uint32_t)__popcll(mk);
+                b[u] = p < T ? p + s_adj[w][row - 1u] : r0;  // (row >= 1 whenever p < T)
+                q[u] = frec[b[u]];
+            }
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) {
+                const uint32_t p = p0 + (uint32_t)u * 64u + ln;
+                const unsigned long long bs = ((unsigned long long)q[u].w << 32) | q[u].z;
+                hit[u] = p < T && b[u] != r0 &&  // (the source is never its own neighbour)
+                         rel(R.x, R.z, R.s, __uint_as_float(q[u].x), __uint_as_float(q[u].y), bs, D);
+            }
+            step(b, q, hit);
+        }
+        __builtin_amdgcn_wave_barrier();  // s_adj is rewritten by the next row group
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    }
+}
+
 template <bool WRITE>
 __device__ __forceinline__ void cast_pass(const CastArgs &A) {
     extern __shared__ uint32_t gcur[];  // [G] count: the block's records per gate; write: next position of its run
-    __shared__ uint32_t s_adj[ST / 64][64];             // candidate index - position, per non-empty row
-    __shared__ uint32_t s_mark[ST / 64][CAST_WU * 64];  // a non-empty row starts at this position
     __shared__ unsigned long long s_tot;
     // queued behind the count pass without a host round trip: nothing to do when the total outgrew
     // the output (the host sees it after its one sync, regrows and relaunches)
@@ -888,10 +960,6 @@ __device__ __forceinline__ void cast_pass(const CastArgs &A) {
     for (uint32_t q = threadIdx.x; q < A.G; q += blockDim.x) gcur[q] = WRITE ? A.blk_cnt[(size_t)q * A.nb + blk] : 0u;
     if (!WRITE && threadIdx.x == 0) s_tot = 0ull;
     __syncthreads();
-    const uint32_t *cs = A.F.cell_start;
-    const uint4 *frec = reinterpret_cast<const uint4 *>(A.F.rec);
-    const unsigned long long lt = (1ull << ln) - 1ull;
-    const unsigned long long le = ln == 63 ? ~0ull : (2ull << ln) - 1ull;
     unsigned long long wtot = 0ull, werr = 0ull;  // (wave-uniform)
     const uint32_t m1 = min(A.n, (blk + 1u) * A.per);
     for (uint32_t m = blk * A.per + w; m < m1; m += ST / 64) {
@@ -930,71 +998,22 @@ __device__ __forceinline__ void cast_pass(const CastArgs &A) {
         const SlotSp S0 = ld_ss(A.F.ss, r0);
         const Rec16 R = ld_rec(A.F.rec, r0);
         if (rfl(S0.slot) != slot) continue;  // left the frame: nilSpace or a space without AOI, no neighbours
-        // the source's go-aoi window (cells), exactly fan_window's: the same float32 margin, in
-        // the source's own space grid
-        const SpaceGrid gr = A.F.grid[rfl(S0.sp)];
-        const float D = gr.D;
-        const float mx = (fabsf(R.x) + 3.0f * D) * 0x1p-20f, mz = (fabsf(R.z) + 3.0f * D) * 0x1p-20f;
-        const int cx0 = cell_of(R.x - D - mx, gr.ox, gr.inv, gr.gx), cx1 = cell_of(R.x + D + mx, gr.ox, gr.inv, gr.gx);
-        const int cz0 = cell_of(R.z - D - mz, gr.oz, gr.inv, gr.gz), cz1 = cell_of(R.z + D + mz, gr.oz, gr.inv, gr.gz);
-        const uint32_t span = rfl((uint32_t)(cx1 - cx0) + 1u), nrows = rfl((uint32_t)(cz1 - cz0) + 1u);
-        const uint32_t row0 = rfl(gr.base + (uint32_t)cz0 * gr.gx + (uint32_t)cx0), gx = rfl(gr.gx);
-        for (uint32_t j0 = 0; j0 < nrows; j0 += 64u) {
-            // lane t: row j0 + t of the window, its candidates [jb, je)
-            const uint32_t t = j0 + ln;
-            const uint32_t rb = row0 + min(t, nrows - 1u) * gx;
-            const uint32_t jb = cs[rb], je = cs[rb + span];
-            const uint32_t len = t < nrows ? je - jb : 0u;
-            const uint32_t incl = wave_scan_add(len);
-            const uint32_t ex = incl - len, T = rdl(incl, 63);
-            const unsigned long long nem = __ballot(len != 0u);
-            if (len) s_adj[w][__popcll(nem & lt)] = jb - ex;
-            for (uint32_t p0 = 0; p0 < T; p0 += CAST_WU * 64u) {
+        // the source's go-aoi window: only hits go on to the receiver's slot, then its gate (and
+        // ClientID); every lane's load is issued (a lane without a hit re-reads the source's)
+        window_walk(A.F, r0, R, S0, w, ln, [&](const uint32_t(&b)[CAST_WU], const uint4(&)[CAST_WU], const bool(&hit)[CAST_WU]) {
+            uint32_t ds[CAST_WU];
+            uint4 st[CAST_WU], ci[CAST_WU];
 #pragma unroll
-                for (int u = 0; u < CAST_WU; ++u) s_mark[w][u * 64 + ln] = 0u;
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                if (len && ex >= p0 && ex - p0 < CAST_WU * 64u) s_mark[w][ex - p0] = 1u;
-                uint32_t nr = (uint32_t)__popcll(__ballot(len != 0u && ex < p0));  // non-empty rows started before this step
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                uint32_t b[CAST_WU];
-                uint4 q[CAST_WU];
-                bool hit[CAST_WU];
+            for (int u = 0; u < CAST_WU; ++u) ds[u] = ld_ss(A.F.ss, hit[u] ? b[u] : r0).slot;
 #pragma unroll
-                for (int u = 0; u < CAST_WU; ++u) {
-                    const unsigned long long mk = __ballot(s_mark[w][u * 64 + ln] != 0u);
-                    const uint32_t p = p0 + (uint32_t)u * 64u + ln;
-                    const uint32_t row = nr + (uint32_t)__popcll(mk & le);  // rows started at or before p
-                    nr += (uint32_t)__popcll(mk);
-                    b[u] = p < T ? p + s_adj[w][row - 1u] : r0;  // (row >= 1 whenever p < T)
-                    q[u] = frec[b[u]];
-                }
-#pragma unroll
-                for (int u = 0; u < CAST_WU; ++u) {
-                    const uint32_t p = p0 + (uint32_t)u * 64u + ln;
-                    const unsigned long long bs = ((unsigned long long)q[u].w << 32) | q[u].z;
-                    hit[u] = p < T && b[u] != r0 &&  // (the source is never its own neighbour)
-                             rel(R.x, R.z, R.s, __uint_as_float(q[u].x), __uint_as_float(q[u].y), bs, D);
-                }
-                // the hits' receivers: slot, then gate (and ClientID), every lane's load issued
-                // (a lane without a hit re-reads the source's)
-                uint32_t ds[CAST_WU];
-                uint4 st[CAST_WU], ci[CAST_WU];
-#pragma unroll
-                for (int u = 0; u < CAST_WU; ++u) ds[u] = ld_ss(A.F.ss, hit[u] ? b[u] : r0).slot;
-#pragma unroll
-                for (int u = 0; u < CAST_WU; ++u) {
-                    st[u] = A.slots[SLOT_U4 * (size_t)ds[u]];
-                    ci[u] = make_uint4(0, 0, 0, 0);
-                    if (WRITE) ci[u] = A.slots[SLOT_U4 * (size_t)ds[u] + 3];
-                }
-#pragma unroll
-                for (int u = 0; u < CAST_WU; ++u) emit(hit[u], st[u].x, ds[u], ci[u]);
+            for (int u = 0; u < CAST_WU; ++u) {
+                st[u] = A.slots[SLOT_U4 * (size_t)ds[u]];
+                ci[u] = make_uint4(0, 0, 0, 0);
+                if (WRITE) ci[u] = A.slots[SLOT_U4 * (size_t)ds[u] + 3];
             }
-            __builtin_amdgcn_wave_barrier();  // s_adj is rewritten by the next row group
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        }
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) emit(hit[u], st[u].x, ds[u], ci[u]);
+        });
     }
     if (WRITE) return;
     if (ln == 0 && wtot) atomicAdd(&s_tot, wtot);
@@ -1009,6 +1028,147 @@ __device__ __forceinline__ void cast_pass(const CastArgs &A) {
 
 __global__ __launch_bounds__(ST) void k_cast_count(CastArgs A) { cast_pass<false>(A); }
 __global__ __launch_bounds__(ST) void k_cast_write(CastArgs A) { cast_pass<true>(A); }
+
+// ------------------------------------------------------ client switch ------
+// Entity.SetClient for a batch (Entity.go:678-724; GiveClientTo, :752-765, is a detach of one
+// entity and an attach of another).  Message m = (slot, new gate index or NO_GATE, new ClientID);
+// the old client is the slot record's.  Unless the two are equal, every B with rel(source, B)
+// (B in the source's InterestedBy, with or without a client) gives a 32-B destroy record {old
+// ClientID, B's EntityID} under the old gate if there was a client, and a 48-B create record
+// {new ClientID, B's EntityID, B's x, y, z, yaw: k_route's} under the new gate if there is one.
+// The broadcast's shape: one wave per message, a block a contiguous chunk, the window walked by
+// both passes (window_walk).  A message's two gates are wave-uniform, so the count pass loads
+// nothing per hit: it adds the popcount of each step's hits in a register and the sum once per
+// message to the block's LDS tables [2][G] (creates, then destroys, as k_route).  One scan
+// over both parts; the write pass reads the split (all creates) from the scanned table.  It
+// takes positions with one LDS atomic per table and wave step (lane 0 adds the popcount, a hit
+// adds its rank among the hits) and only then loads B's slot, EntityID and position record.
+// The clients themselves are changed after the write pass (k_switch_apply, from the same upload).
+struct SwitchArgs {
+    FrameView F;
+    SlotTab info;
+    const uint4 *slots;      // SLOT_U4 per slot: sst, pos, eid, cid
+    const uint4 *m_cid;      // the messages' new ClientIDs
+    const uint32_t *m_slot;  // their slots
+    const uint32_t *m_gate;  // their new gate indices (NO_GATE: detach)
+    uint32_t n;
+    uint32_t G, nb, per;  // gates, blocks, messages per block
+    uint32_t *blk_cnt;    // [2][G][nb]: creates then destroys (the scan turns it into bases)
+    unsigned long long *sc;  // {create, destroy} records of all blocks (64-bit: the scan's total wraps)
+    uint4 *out_c;            // 3 uint4 per create record
+    uint4 *out_d;            // 2 uint4 per destroy record
+    unsigned long long cap_c, cap_d;  // records they hold (the write pass writes nothing past a larger total)
+};
+
+template <bool WRITE>
+__device__ __forceinline__ void switch_pass(const SwitchArgs &A) {
+    extern __shared__ uint32_t gtab[];  // [2][G] count: the block's records; write: next position of each run
+    __shared__ unsigned long long s_tot[2];
+    if (WRITE && (A.sc[0] > A.cap_c || A.sc[1] > A.cap_d)) return;  // (as cast_pass: the host regrows and relaunches)
+    const uint32_t blk = blockIdx.x, w = threadIdx.x / 64, ln = s_lane();
+    for (uint32_t q = threadIdx.x; q < 2 * A.G; q += blockDim.x) gtab[q] = WRITE ? A.blk_cnt[(size_t)q * A.nb + blk] : 0u;
+    if (!WRITE && threadIdx.x < 2) s_tot[threadIdx.x] = 0ull;
+    __syncthreads();
+    const uint32_t split = WRITE ? A.blk_cnt[(size_t)A.G * A.nb] : 0u;  // destroy bases start here
+    const unsigned long long lt = (1ull << ln) - 1ull;
+    unsigned long long wtot_c = 0ull, wtot_d = 0ull;  // (wave-uniform)
+    const uint32_t m1 = min(A.n, (blk + 1u) * A.per);
+    for (uint32_t m = blk * A.per + w; m < m1; m += ST / 64) {
+        // the message and the source: its frame index, old gate and old ClientID in one round trip
+        const uint32_t slot = rfl(A.m_slot[m]), gnew = rfl(A.m_gate[m]);
+        const uint4 cm = A.m_cid[m];
+        const uint4 cnew = make_uint4(rfl(cm.x), rfl(cm.y), rfl(cm.z), rfl(cm.w));
+        const uint32_t r0 = rfl(A.info.rank[slot]);
+        const uint4 st0 = A.slots[SLOT_U4 * (size_t)slot];
+        const uint4 co = A.slots[SLOT_U4 * (size_t)slot + 3];
+        const uint32_t gold = rfl(st0.x);
+        const uint4 cold = make_uint4(rfl(co.x), rfl(co.y), rfl(co.z), rfl(co.w));
+        const bool had = gold < A.G, has = gnew < A.G;  // (NO_GATE: no client)
+        if (had == has && (!has || (gold == gnew && eq4(cold, cnew)))) continue;  // oldClient == client (Entity.go:680)
+        if (r0 >= A.F.n) continue;  // (rank: 0xFFFFFFFF if never live)
+        const SlotSp S0 = ld_ss(A.F.ss, r0);
+        const Rec16 R = ld_rec(A.F.rec, r0);
+        if (rfl(S0.slot) != slot) continue;  // left the frame: nilSpace or a space without AOI, no neighbours
+        uint32_t nhit = 0;  // (wave-uniform)
+        // a hit's records at its positions: B's EntityID e, slot position record P, frame record fr
+        auto put = [&](bool v, uint32_t p_c, uint32_t p_d, const uint4 &e, const uint4 &P, const uint4 &fr) {
+            if (v && has && p_c < A.cap_c) {  // x, z of the frame; y, yaw of the slot (k_route's create)
+                uint4 *o = A.out_c + 3 * (size_t)p_c;
+                o[0] = cnew;
+                o[1] = make_uint4(e.x, e.y, e.z, e.w);  // (by component: a whole-vector copy to both records kept the array in scratch)
+                o[2] = make_uint4(fr.x, P.y, fr.y, P.w);
+            }
+            if (v && had && p_d < A.cap_d) {
+                uint4 *o = A.out_d + 2 * (size_t)p_d;
+                o[0] = cold;
+                o[1] = make_uint4(e.x, e.y, e.z, e.w);
+            }
+        };
+        window_walk(A.F, r0, R, S0, w, ln, [&](const uint32_t(&b)[CAST_WU], const uint4(&q)[CAST_WU], const bool(&hit)[CAST_WU]) {
+            if (!WRITE) {
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) nhit += (uint32_t)__popcll(__ballot(hit[u]));
+                return;
+            }
+            // positions: one atomic per table for the step's hits, a hit takes its rank among them
+            uint32_t pc[CAST_WU], pd[CAST_WU];
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) {
+                const unsigned long long hb = __ballot(hit[u]);
+                const uint32_t c = (uint32_t)__popcll(hb), rk = (uint32_t)__popcll(hb & lt);
+                uint32_t bc = 0, bd = 0;
+                if (ln == 0 && c) {
+                    if (has) bc = atomicAdd(&gtab[gnew], c);
+                    if (had) bd = atomicAdd(&gtab[A.G + gold], c);
+                }
+                pc[u] = rfl(bc) + rk;
+                pd[u] = rfl(bd) - split + rk;
+            }
+            // the hits' EntityID and position record; every lane's load is issued (a lane without a
+            // hit re-reads the source's)
+            uint32_t ds[CAST_WU];
+            uint4 ei[CAST_WU], po[CAST_WU];
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) ds[u] = ld_ss(A.F.ss, hit[u] ? b[u] : r0).slot;
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) {
+                po[u] = A.slots[SLOT_U4 * (size_t)ds[u] + 1];
+                ei[u] = A.slots[SLOT_U4 * (size_t)ds[u] + 2];
+            }
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) put(hit[u], pc[u], pd[u], ei[u], po[u], q[u]);
+        });
+        if (!WRITE && nhit) {
+            if (has) wtot_c += nhit;
+            if (had) wtot_d += nhit;
+            if (ln == 0) {
+                if (has) atomicAdd(&gtab[gnew], nhit);
+                if (had) atomicAdd(&gtab[A.G + gold], nhit);
+            }
+        }
+    }
+    if (WRITE) return;
+    if (ln == 0 && wtot_c) atomicAdd(&s_tot[0], wtot_c);
+    if (ln == 0 && wtot_d) atomicAdd(&s_tot[1], wtot_d);
+    __syncthreads();
+    for (uint32_t q = threadIdx.x; q < 2 * A.G; q += blockDim.x) A.blk_cnt[(size_t)q * A.nb + blk] = gtab[q];
+    if (threadIdx.x < 2 && s_tot[threadIdx.x]) atomicAdd(&A.sc[threadIdx.x], s_tot[threadIdx.x]);  // two per block
+    if (threadIdx.x == 0 && blk == 0) A.blk_cnt[2 * (size_t)A.G * A.nb] = 0u;  // the scan's last entry: the (32-bit) total
+}
+
+__global__ __launch_bounds__(ST) void k_switch_count(SwitchArgs A) { switch_pass<false>(A); }
+__global__ __launch_bounds__(ST) void k_switch_write(SwitchArgs A) { switch_pass<true>(A); }
+
+// The switch itself, from the uploaded messages: what gwaoi_entity_set_client leaves (a detach
+// keeps the ClientID and clears the gate).  The slots of a batch are distinct.
+__global__ void k_switch_apply(const uint4 *__restrict__ m_cid, const uint32_t *__restrict__ m_slot,
+                               const uint32_t *__restrict__ m_gate, uint32_t n, uint4 *slots) {
+    const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n) return;
+    const uint32_t s = m_slot[m], g = m_gate[m];
+    if (g != NO_GATE) slots[SLOT_U4 * (size_t)s + 3] = m_cid[m];
+    reinterpret_cast<uint32_t *>(slots)[SLOT_W * (size_t)s + SST_GATE] = g;
+}
 
 // -------------------------------------------------------------- route ------
 struct RouteArgs {
@@ -1143,6 +1303,15 @@ struct SyncState {
     DevBuf<uint4> cast_out;
     PinnedBuf<uint8_t> h_cast;
     std::vector<uint64_t> h_off_cast;
+    // client-switch collect: the 64-bit totals {creates, destroys}, outputs of its own (valid until
+    // the next switch collect) and a per-slot stamp that finds a slot named twice in one batch
+    DevBuf<unsigned long long> sw_sc;
+    PinnedBuf<unsigned long long> h_sw_sc;
+    DevBuf<uint4> sw_out_c, sw_out_d;
+    PinnedBuf<uint8_t> h_sw_c, h_sw_d;
+    std::vector<uint64_t> h_off_swc, h_off_swd;
+    std::vector<uint32_t> sw_stamp, sw_gate;  // sw_gate: the batch's new gate indices
+    uint32_t sw_epoch = 0;
 };
 
 namespace {
@@ -1665,6 +1834,159 @@ int collect_cast(gwaoi_world *w, const uint32_t *slots, const uint32_t *flags, s
     return status;
 }
 
+// gwaoi_collect_client_switch: messages (slots[m], gate_ids[m], clientids[16m..16m+16)) in host
+// memory.  Reads the relation of the last flush and the clients on the device; the clients are
+// switched behind the write pass.  Every error is found before anything changes.
+int collect_switch(gwaoi_world *w, const uint32_t *slots, const uint16_t *gate_ids, const uint8_t *clientids, size_t n,
+                   gwaoi_gate_records *creates, gwaoi_gate_records *destroys) {
+    if (!w || !creates || !destroys || (n && (!slots || !gate_ids))) return GWAOI_EINVAL;
+    SyncState *S;
+    if (int rc = state(w, &S)) return rc;
+    const WorldView v = world_view(w);
+    if (v.pending_ops) return GWAOI_ESTATE;
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    for (size_t m = 0; m < n; ++m)
+        if (slots[m] >= S->max_slots) return GWAOI_EBADSLOT;
+    if (S->sw_stamp.empty()) S->sw_stamp.assign(S->max_slots, 0u);
+    if (++S->sw_epoch == 0) {  // (the stamps of 2^32 calls ago)
+        std::fill(S->sw_stamp.begin(), S->sw_stamp.end(), 0u);
+        S->sw_epoch = 1;
+    }
+    for (size_t m = 0; m < n; ++m) {
+        if (S->sw_stamp[slots[m]] == S->sw_epoch) return GWAOI_EINVAL;  // a slot named twice: the caller splits the batch
+        S->sw_stamp[slots[m]] = S->sw_epoch;
+    }
+    // the new clients' gate indices; gates the world has not seen are registered only once the
+    // whole batch is known to fit
+    const uint32_t G0 = (uint32_t)S->gate_ids.size();
+    std::vector<uint16_t> fresh;
+    std::unordered_map<uint32_t, uint32_t> fresh_idx;
+    static const uint8_t zero_id[GWAOI_ID_LEN] = {0};
+    S->sw_gate.assign(n, NO_GATE);
+    for (size_t m = 0; m < n; ++m) {
+        if (!clientids || !std::memcmp(clientids + GWAOI_ID_LEN * m, zero_id, GWAOI_ID_LEN)) continue;  // no client
+        auto it = S->gate_idx.find(gate_ids[m]);
+        if (it != S->gate_idx.end()) {
+            S->sw_gate[m] = it->second;
+            continue;
+        }
+        auto ins = fresh_idx.emplace(gate_ids[m], G0 + (uint32_t)fresh.size());
+        if (ins.second) fresh.push_back(gate_ids[m]);
+        S->sw_gate[m] = ins.first->second;
+    }
+    if (G0 + fresh.size() > GWAOI_MAX_GATES) return GWAOI_ECAPACITY;
+    if (int rc = push(S)) return rc;  // every earlier gwaoi_entity_set_client is visible to the passes
+    for (uint16_t id : fresh) {
+        S->gate_idx.emplace(id, (uint32_t)S->gate_ids.size());
+        S->gate_ids.push_back(id);
+    }
+    const uint32_t G = (uint32_t)S->gate_ids.size();
+    uint64_t nc = 0, nd = 0;
+    SwitchArgs A{};
+    auto records = [&]() -> int {  // the two outputs on the device and their offsets; changes no state
+        S->h_off_swc.assign((size_t)G + 1, 0);
+        S->h_off_swd.assign((size_t)G + 1, 0);
+        if (G && n) {
+            // the messages, uploaded once: new ClientIDs, slots, new gate indices
+            const size_t bytes = n * (sizeof(uint4) + 8);
+            if (int rc = ensure_stage(S, bytes)) return rc;
+            char *h = S->h_stage, *d = S->d_stage;
+            if (clientids)
+                std::memcpy(h, clientids, n * 16);
+            else
+                std::memset(h, 0, n * 16);
+            std::memcpy(h + n * 16, slots, n * 4);
+            std::memcpy(h + n * 20, S->sw_gate.data(), n * 4);
+            HIP_TRY(S->w, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, S->st));
+            HIP_TRY(S->w, hipEventRecord(S->stage_ev, S->st));
+            S->stage_pending = true;
+            A.F = v.F;
+            A.info = v.info;
+            A.slots = S->slots;
+            A.m_cid = reinterpret_cast<const uint4 *>(d);
+            A.m_slot = reinterpret_cast<const uint32_t *>(d + n * 16);
+            A.m_gate = reinterpret_cast<const uint32_t *>(d + n * 20);
+            A.n = (uint32_t)n;
+            // the broadcast's grid: a block loops over a contiguous chunk of messages, capped so that
+            // the [2][G][nb] table stays bounded
+            A.per = std::max<uint32_t>(ST / 64, (cdivu(n, CAST_MAX_BLOCKS) + ST / 64 - 1) / (ST / 64) * (ST / 64));
+            A.nb = cdivu(n, A.per);
+            A.G = G;
+            if (int rc = ensure_u32(S, S->blk_cnt, 2 * (size_t)G * A.nb + 1)) return rc;
+            A.blk_cnt = S->blk_cnt;
+            if (!S->sw_sc)
+                if (int rc = alloc_all(S->w, S->sw_sc, 2)) return rc;
+            if (!S->h_sw_sc)
+                if (int rc = alloc_pinned(S->w, S->h_sw_sc, 2)) return rc;
+            A.sc = S->sw_sc;
+            const size_t lds = 2 * (size_t)G * 4;
+            HIP_TRY(S->w, hipMemsetAsync(S->sw_sc, 0, 16, S->st));
+            k_switch_count<<<A.nb, ST, lds, S->st>>>(A);
+            HIP_TRY(S->w, hipGetLastError());
+            // as the broadcast: the bases are scanned and the write pass queued with the outputs as
+            // they are (the last switch's sizes) before the one host wait, which brings the per-gate
+            // bases and the two 64-bit totals
+            if (int rc = part_bases(S, 2 * G, A.nb, false, false)) return rc;
+            auto write = [&]() -> int {
+                A.out_c = S->sw_out_c;
+                A.out_d = S->sw_out_d;
+                A.cap_c = S->sw_out_c.cap() / 3;
+                A.cap_d = S->sw_out_d.cap() / 2;
+                k_switch_write<<<A.nb, ST, lds, S->st>>>(A);
+                HIP_TRY(S->w, hipGetLastError());
+                return GWAOI_OK;
+            };
+            const bool queued = S->sw_out_c.cap() && S->sw_out_d.cap();
+            if (queued)
+                if (int rc = write()) return rc;
+            if (int rc = fetch_bases(S, 2 * G, false)) return rc;
+            HIP_TRY(S->w, hipMemcpyAsync(S->h_sw_sc, S->sw_sc, 16, hipMemcpyDeviceToHost, S->st));
+            HIP_TRY(S->w, hipStreamSynchronize(S->st));
+            unpack_bases(S, 2 * G);
+            nc = S->h_sw_sc[0];
+            nd = S->h_sw_sc[1];
+            if (nc + nd > 0xFFFFFFFFull) {  // (either kind alone, or the two in their one index space)
+                world_set_error(w, "sync: a client switch of more than 2^32 - 1 records");
+                return GWAOI_ECAPACITY;
+            }
+            if (!queued || nc > A.cap_c || nd > A.cap_d) {  // (first switch, or more records than an output holds)
+                if (int rc = ensure_out(S, S->sw_out_c, 3 * std::max<uint64_t>(nc, 1))) return rc;
+                if (int rc = ensure_out(S, S->sw_out_d, 2 * std::max<uint64_t>(nd, 1))) return rc;
+                if (nc + nd)
+                    if (int rc = write()) return rc;
+            }
+            const uint64_t split = S->h_off_raw[G];  // creates occupy [0, split) of one index space
+            for (uint32_t g = 0; g <= G; ++g) {
+                S->h_off_swc[g] = S->h_off_raw[g];
+                S->h_off_swd[g] = S->h_off_raw[G + g] - split;
+            }
+        }
+        if (int rc = ensure_out(S, S->sw_out_c, 3)) return rc;  // (an empty result's pointers)
+        if (int rc = ensure_out(S, S->sw_out_d, 2)) return rc;
+        if (int rc = ensure_host(S, S->h_sw_c, std::max<uint64_t>(nc, 1) * GWAOI_SYNC_OUT_REC)) return rc;
+        return ensure_host(S, S->h_sw_d, std::max<uint64_t>(nd, 1) * GWAOI_DESTROY_REC);
+    };
+    if (int rc = records()) {  // nothing is changed: the batch's gates go again
+        for (uint16_t id : fresh) S->gate_idx.erase(id);
+        S->gate_ids.resize(G0);
+        return rc;
+    }
+    if (nc) HIP_TRY(S->w, hipMemcpyAsync(S->h_sw_c, S->sw_out_c, nc * GWAOI_SYNC_OUT_REC, hipMemcpyDeviceToHost, S->st));
+    if (nd) HIP_TRY(S->w, hipMemcpyAsync(S->h_sw_d, S->sw_out_d, nd * GWAOI_DESTROY_REC, hipMemcpyDeviceToHost, S->st));
+    // the switch itself, behind the write pass on the same stream: what n gwaoi_entity_set_client
+    // calls would have left.  (Without a gate no slot ever had a client and the batch attaches
+    // none: nothing to write.)
+    if (G && n) {
+        k_switch_apply<<<cdivu(n, ST), ST, 0, S->st>>>(A.m_cid, A.m_slot, A.m_gate, A.n, S->slots);
+        HIP_TRY(S->w, hipGetLastError());
+    }
+    for (size_t m = 0; m < n; ++m) S->h_client[slots[m]] = S->sw_gate[m] != NO_GATE;
+    HIP_TRY(S->w, hipStreamSynchronize(S->st));
+    fill_out(S, creates, S->h_off_swc, S->h_sw_c);
+    fill_out(S, destroys, S->h_off_swd, S->h_sw_d);
+    return GWAOI_OK;
+}
+
 int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
     if (!w || (n && !payload)) return GWAOI_EINVAL;
     if (on_device && (reinterpret_cast<uintptr_t>(payload) & 15u)) return GWAOI_EINVAL;
@@ -1945,6 +2267,14 @@ int gwaoi_collect_broadcast_device(gwaoi_world *w, const uint32_t *d_slots, cons
                                    gwaoi_gate_records *out) {
     return gw::api_guard([&]() -> int {
     return gw::collect_cast(w, d_slots, d_flags, n, out, true);
+    });
+}
+
+int gwaoi_collect_client_switch(gwaoi_world *w, const uint32_t *slots, const uint16_t *gate_ids,
+                                const uint8_t *clientids, size_t n, gwaoi_gate_records *creates,
+                                gwaoi_gate_records *destroys) {
+    return gw::api_guard([&]() -> int {
+    return gw::collect_switch(w, slots, gate_ids, clientids, n, creates, destroys);
     });
 }
 

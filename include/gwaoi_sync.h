@@ -25,6 +25,9 @@
  *     sendMapAttrClearToClients / sendListAttrChangeToClients /    caller attaches the RPC or
  *     sendListAttrPopToClients / sendListAttrAppendToClients       attribute payload per record)
  *     for AllClients attributes         Entity.go:814-917
+ *   Entity.SetClient                    Entity.go:678-724       gwaoi_collect_client_switch
+ *   Entity.GiveClientTo                 Entity.go:752-765         (the create / destroy lists of the
+ *                                                                  entities in InterestedBy, and the switch)
  *
  * Entity ids and client ids are the reference's 16-byte strings
  * (common.ENTITYID_LENGTH = common.CLIENTID_LENGTH = uuid.UUID_LENGTH = 16,
@@ -182,6 +185,60 @@ int gwaoi_collect_broadcast(gwaoi_world *w, const uint32_t *slots, const uint32_
 /* Same; messages in device memory, records stay in device memory. */
 int gwaoi_collect_broadcast_device(gwaoi_world *w, const uint32_t *d_slots, const uint32_t *d_flags, size_t n,
                                    gwaoi_gate_records *out);
+
+/* ---- client switches ------------------------------------------------------- */
+/* Entity.SetClient for a batch of n entities (Entity.go:678-724; GiveClientTo,
+ * Entity.go:752-765, is a detach of one entity and an attach of another): the
+ * destroy records the old clients and the create records the new clients get
+ * for the entities in each source's InterestedBy, per gate, and the switch.
+ *
+ * Messages.  Message m sets the client of slots[m] to (gate_ids[m],
+ * clientids[16m .. 16m+16)).  An all-zero ClientID, or clientids == NULL,
+ * means no client (GoWorld ids are 16 printable bytes); gate_ids[m] is then
+ * ignored.  gwaoi_entity_set_client is unchanged.  A slot may appear at most
+ * once per call: a repeat is GWAOI_EINVAL and the caller splits the batch
+ * (with distinct slots the array order is irrelevant).
+ * Old client.  Read from the world's state on the device: every earlier
+ * gwaoi_entity_set_client is visible (the call pushes the pending host writes
+ * first, as the collects do).
+ * No-op.  A message whose new (gate, ClientID) equals the current one, or that
+ * detaches an entity without a client, yields nothing (the reference's
+ * `oldClient == client` return).
+ * Destroy records (GWAOI_DESTROY_REC, 32 B: old ClientID, neighbour EntityID):
+ * one per b with rel(src, b) (b in src's InterestedBy), under the old client's
+ * gate; only if there was an old client.
+ * Create records (GWAOI_SYNC_OUT_REC, 48 B: new ClientID, neighbour EntityID,
+ * b's x, y, z, yaw): one per b with rel(src, b), under the new client's gate;
+ * only if there is a new client.  x and z are the frame's, y and yaw the
+ * slot's position record: exactly gwaoi_collect_client_events' create record.
+ * Neighbours.  Whether b has a client is irrelevant; the source is never its
+ * own neighbour.
+ * What the caller still sends itself.  The entity's own create (isPlayer), its
+ * own destroy and the Space entity's record (Entity.go:692-708) are host
+ * state.  On a client the order is: all destroy records of the call, then the
+ * caller's own / space records, then all create records; that keeps the
+ * reference's order per client.
+ * Relation.  That of the last committed flush: GWAOI_ESTATE with ops queued or
+ * a flush in flight, as for the collects.
+ * Sources outside the frame (nilSpace, a space without AOI, a slot never bound
+ * or entered) produce no records; their client is still switched.
+ * State.  After the call each slot's gate and ClientID are what n
+ * gwaoi_entity_set_client calls would have left (gate ids not seen before are
+ * registered).  Sync flags, positions and the relation are untouched.
+ * Output.  Both results are filled as for the other collects, with buffers of
+ * their own: valid until the next switch collect.  Records are in host memory,
+ * in an unspecified order within a gate; the multiset per gate is exact.
+ * n == 0 gives two empty results and GWAOI_OK.  More than 2^32 - 1 records of
+ * either kind (the two share one 32-bit index space: or of both together)
+ * give GWAOI_ECAPACITY.
+ * Errors.  On any error nothing is produced and nothing is changed.  Null w,
+ * creates or destroys, or null slots / gate_ids with n > 0: GWAOI_EINVAL; a
+ * slot >= max_slots: GWAOI_EBADSLOT; a repeated slot: GWAOI_EINVAL; a batch
+ * that would take the world past GWAOI_MAX_GATES distinct gates:
+ * GWAOI_ECAPACITY, checked before any gate is registered. */
+int gwaoi_collect_client_switch(gwaoi_world *w, const uint32_t *slots, const uint16_t *gate_ids,
+                                const uint8_t *clientids /* 16 B per message, NULL: all detach */,
+                                size_t n, gwaoi_gate_records *creates, gwaoi_gate_records *destroys);
 
 #ifdef __cplusplus
 }
