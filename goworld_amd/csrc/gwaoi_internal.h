@@ -251,7 +251,10 @@ void launch_keygen(Rec16 *s_rec, const SlotSp *s_ss, uint32_t n_total, const Spa
                    uint32_t sentinel, uint32_t *keys, uint32_t *vals, const Rec16 *p_rec, const SlotSp *p_ss,
                    const SpaceGrid *p_grid, uint32_t n_prev, float *blk, TickScalars *sc, const uint32_t *p_key,
                    unsigned long long *cnt64, uint64_t seq_base, uint32_t *special, const TickZero &tz,
-                   unsigned long long *tent, hipStream_t st);
+                   unsigned long long *tent, bool deep, hipStream_t st);
+// deep (here and in incremental_sort, the same value for one flush: keygen's partials are per
+// block): the flush's early kernels run beside the previous flush's combined pass (FlushPlan::ovl);
+// keygen then takes GWAOI_KG_PER_DEEP entries per thread.
 // special (optional, cdiv(n_prev, TILE_A) words): keygen marks the previous-frame tiles that hold an
 // entity the special pass must look at; launch_pairs skips the others.
 // The stable sort of S' by key when the grid is the previous frame's: the
@@ -306,7 +309,7 @@ void incremental_sort(const uint32_t *keys, uint32_t n_total, uint32_t n_prev, c
                       const uint32_t *p_cell_start, unsigned long long *cnt64, uint32_t total_cells,
                       uint32_t sentinel, uint32_t *cell_start, uint32_t *arr_pos, uint32_t *arr_idx,
                       unsigned long long *tmp, uint32_t *perm, uint32_t *skeys, const float *blk,
-                      TickScalars *sc, const SpecialJob *sp, const GatherJob *gj, hipStream_t st);
+                      TickScalars *sc, const SpecialJob *sp, const GatherJob *gj, bool deep, hipStream_t st);
 // LSD radix sort of (key,val) pairs on `bits` low key bits.  Returns which
 // buffer (0 or 1) holds the result.
 struct SortBuffers {

@@ -410,11 +410,17 @@ constexpr int S64_TILE = SC_T * S64_I;
 #ifndef GWAOI_KG_PER
 #define GWAOI_KG_PER 2  // S' entries per keygen thread (their operands in flight together)
 #endif
-constexpr int KG_PER = GWAOI_KG_PER;
-static_assert(KG_PER == 1 || KG_PER == 2, "the written-entry count below takes one or two entries per thread");
-constexpr uint32_t keygen_blocks(uint32_t n) { return (n + 256u * KG_PER - 1) / (256u * KG_PER); }
+// ... of an overlapped flush's keygen (launch_keygen's deep), which runs beside the previous flush's
+// k_combined: half the workgroups to get onto the CUs that pass holds.  68 VGPRs, the room one
+// retiring k_combined workgroup leaves (72 per lane); 8 entries (131 VGPRs) lost, DESIGN.md §3.
+#ifndef GWAOI_KG_PER_DEEP
+#define GWAOI_KG_PER_DEEP 4
+#endif
+constexpr uint32_t keygen_blocks(uint32_t n, bool deep) {
+    return (n + 256u * (deep ? GWAOI_KG_PER_DEEP : GWAOI_KG_PER) - 1) / (256u * (deep ? GWAOI_KG_PER_DEEP : GWAOI_KG_PER));
+}
 
-template <bool INCR>
+template <bool INCR, int KG_PER>
 __global__ __launch_bounds__(256) void k_keygen(Rec16 *s_rec, const SlotSp *__restrict__ s_ss,
                                                 uint32_t n, const SpaceGrid *__restrict__ grid, uint32_t sentinel,
                                                 uint32_t *keys, uint32_t *vals, const Rec16 *__restrict__ p_rec,
@@ -546,9 +552,13 @@ __global__ __launch_bounds__(256) void k_keygen(Rec16 *s_rec, const SlotSp *__re
         dr = fmaxf(dr, __shfl_xor(dr, o));
         bm = fmaxf(bm, __shfl_xor(bm, o));
     }
+    __shared__ uint32_t s_nw[256 / WAVE];  // each wave's written entries (summed behind the barriers below)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nwr += __shfl_xor(nwr, o);
     if (lane() == 0) {
         s_m[0][threadIdx.x / WAVE] = dr;
         s_m[1][threadIdx.x / WAVE] = bm;
+        s_nw[threadIdx.x / WAVE] = nwr;
     }
     // the special pass's tiles of this block (previous-frame entries [256 t, 256 t + 256)): does one
     // hold an entity that is not near (left, changed space, jumped)?  k_pairs<1> skips the tiles without
@@ -558,7 +568,6 @@ __global__ __launch_bounds__(256) void k_keygen(Rec16 *s_rec, const SlotSp *__re
         const bool sp_any = __syncthreads_or(base + 256u * (uint32_t)u < n_prev && !near[u]);
         if (special && threadIdx.x == 0 && t * 256u < n_prev) special[t] = sp_any ? 1u : 0u;
     }
-    const uint32_t nw = (uint32_t)__syncthreads_count(nwr >= 1) + (KG_PER > 1 ? (uint32_t)__syncthreads_count(nwr >= 2) : 0u);
     if (INCR && threadIdx.x == 0) {  // the block's (tile, count) notes, one add per distinct tile
         uint32_t t = 0xFFFFFFFFu, c = 0u;
         for (int u = 0; u < KG_PER; ++u)  // (entry order: the notes of one tile come together)
@@ -575,12 +584,14 @@ __global__ __launch_bounds__(256) void k_keygen(Rec16 *s_rec, const SlotSp *__re
         if (c) atomicAdd(&tent[t], (unsigned long long)c);
     }
     if (threadIdx.x == 0) {
-        reinterpret_cast<uint32_t *>(blk)[2 * gridDim.x + blockIdx.x] = nw;
         float a = s_m[0][0], b = s_m[1][0];
+        uint32_t nw = s_nw[0];
         for (int q = 1; q < 256 / WAVE; ++q) {
             a = fmaxf(a, s_m[0][q]);
             b = fmaxf(b, s_m[1][q]);
+            nw += s_nw[q];
         }
+        reinterpret_cast<uint32_t *>(blk)[2 * gridDim.x + blockIdx.x] = nw;
         blk[2 * blockIdx.x] = a;
         blk[2 * blockIdx.x + 1] = b;
     }
@@ -3361,19 +3372,23 @@ void launch_keygen(Rec16 *s_rec, const SlotSp *s_ss, uint32_t n_total, const Spa
                    uint32_t sentinel, uint32_t *keys, uint32_t *vals, const Rec16 *p_rec, const SlotSp *p_ss,
                    const SpaceGrid *p_grid, uint32_t n_prev, float *blk, TickScalars *sc, const uint32_t *p_key,
                    unsigned long long *cnt64, uint64_t seq_base, uint32_t *special, const TickZero &tz,
-                   unsigned long long *tent, hipStream_t st) {
+                   unsigned long long *tent, bool deep, hipStream_t st) {
     if (!n_total) {  // no entry: only the fold (d_rel = bmax = 0; a unique-moves apply's dropped ops and
                      // errors reach sc->err, and its error word and drop count are reset for the next flush)
         k_keygen_reduce<<<1, 1024, 0, st>>>(blk, 0u, sc);
         return;
     }
-    const uint32_t nb = keygen_blocks(n_total);
-    if (cnt64)
-        k_keygen<true><<<nb, 256, 0, st>>>(s_rec, s_ss, n_total, grid, sentinel, keys, vals, p_rec, p_ss, p_grid,
-                                           n_prev, blk, p_key, cnt64, seq_base, special, tz, tent);  // folded by incremental_sort
+    deep = deep && cnt64;  // (an overlapped flush is incremental)
+    const uint32_t nb = keygen_blocks(n_total, deep);
+    if (deep)
+        k_keygen<true, GWAOI_KG_PER_DEEP><<<nb, 256, 0, st>>>(s_rec, s_ss, n_total, grid, sentinel, keys, vals, p_rec, p_ss,
+                                                              p_grid, n_prev, blk, p_key, cnt64, seq_base, special, tz, tent);
+    else if (cnt64)
+        k_keygen<true, GWAOI_KG_PER><<<nb, 256, 0, st>>>(s_rec, s_ss, n_total, grid, sentinel, keys, vals, p_rec, p_ss, p_grid,
+                                                         n_prev, blk, p_key, cnt64, seq_base, special, tz, tent);  // folded by incremental_sort
     else {
-        k_keygen<false><<<nb, 256, 0, st>>>(s_rec, s_ss, n_total, grid, sentinel, keys, vals, p_rec, p_ss, p_grid,
-                                            n_prev, blk, nullptr, nullptr, seq_base, special, tz, nullptr);
+        k_keygen<false, GWAOI_KG_PER><<<nb, 256, 0, st>>>(s_rec, s_ss, n_total, grid, sentinel, keys, vals, p_rec, p_ss, p_grid,
+                                                          n_prev, blk, nullptr, nullptr, seq_base, special, tz, nullptr);
         k_keygen_reduce<<<1, 1024, 0, st>>>(blk, nb, sc);
     }
 }
@@ -3384,7 +3399,7 @@ void incremental_sort(const uint32_t *keys, uint32_t n_total, uint32_t n_prev, c
                       const uint32_t *p_cell_start, unsigned long long *cnt64, uint32_t total_cells,
                       uint32_t sentinel, uint32_t *cell_start, uint32_t *arr_pos, uint32_t *arr_idx,
                       unsigned long long *tmp, uint32_t *perm, uint32_t *skeys, const float *blk,
-                      TickScalars *sc, const SpecialJob *sp, const GatherJob *gj, hipStream_t st) {
+                      TickScalars *sc, const SpecialJob *sp, const GatherJob *gj, bool deep, hipStream_t st) {
     const size_t m = (size_t)total_cells + 1;
     const uint32_t nb = cdiv(m, S64_TILE);
     uint32_t *shift = arr_pos + m;  // the caller allocates arr_pos with 3 (total_cells + 1) words
@@ -3392,7 +3407,7 @@ void incremental_sort(const uint32_t *keys, uint32_t n_total, uint32_t n_prev, c
     unsigned long long *tcnt = tmp + nb;
     unsigned long long *tent = tmp;  // keygen's entries per tile (incr_keygen_tiles)
     k_scan64<<<nb + 1, SC_T, 0, st>>>(cnt64, m, nb, tent, cell_start, arr_pos, blk,
-                                      keygen_blocks(n_total), sc, p_cell_start, shift, list, tcnt);
+                                      keygen_blocks(n_total, deep), sc, p_cell_start, shift, list, tcnt);
     if (sp && sp->n_tiles) {
         const SpecialJob &J = *sp;
         k_arrive_special<<<J.n_tiles + cdiv(n_total, PT), PT, 0, st>>>(J, keys, n_total, n_prev, p_key, sentinel, arr_pos,

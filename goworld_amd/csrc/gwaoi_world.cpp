@@ -1050,7 +1050,7 @@ int flush_keys_sort(gwaoi_world *w, FlushSet &S, DevFrame &P, DevFrame &Fn, cons
     stage_begin(w, S, ST_KEYGEN);
     gw::launch_keygen(S.srec, s_ss_view(S, P, plan), plan.n_total, Fn.grid, total_cells, w->keys[0], w->vals[0], P.rec,
                       P.ss, P.grid, n_prev, w->blk, S.sc, P.key, plan.incr ? w->cnt64.get() : nullptr, plan.seq_base,
-                      w->special, tz, plan.incr ? w->scan64_tmp.get() : nullptr, st);
+                      w->special, tz, plan.incr ? w->scan64_tmp.get() : nullptr, plan.ovl, st);
     stage_end(w, S, ST_KEYGEN);
     stage_begin(w, S, ST_SORT);
     int which = 1;
@@ -1064,7 +1064,7 @@ int flush_keys_sort(gwaoi_world *w, FlushSet &S, DevFrame &P, DevFrame &Fn, cons
         gw::incremental_sort(w->keys[0], plan.n_total, n_prev, P.key, P.cell_start, w->cnt64, total_cells,
                              total_cells, Fn.cell_start, w->arr_pos, w->arr_idx, w->scan64_tmp, w->vals[1],
                              Fn.key, w->blk, S.sc, plan.sp_fused ? &spj : nullptr, plan.ga_fused ? &gj : nullptr,
-                             st);  // the sorted keys ARE the frame's
+                             plan.ovl, st);  // the sorted keys ARE the frame's
     } else {
         gw::SortBuffers sb{{w->keys[0], w->keys[1]}, {w->vals[0], w->vals[1]}, w->hist, w->scan_tmp};
         which = gw::radix_sort(sb, plan.n_total, bitlen(total_cells), st);
