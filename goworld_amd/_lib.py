@@ -70,7 +70,9 @@ SYNC_EXPORTS = [
     "gwaoi_sync_from_clients", "gwaoi_sync_from_clients_device", "gwaoi_collect_sync_infos",
     "gwaoi_collect_sync_infos_device", "gwaoi_collect_client_events", "gwaoi_entity_enter_plain",
     "gwaoi_entity_leave_plain", "gwaoi_collect_broadcast", "gwaoi_collect_broadcast_device",
-    "gwaoi_collect_client_switch",
+    "gwaoi_collect_client_switch", "gwaoi_neighbors_batch", "gwaoi_neighbors_batch_device",
+    "gwaoi_related_batch", "gwaoi_related_batch_device", "gwaoi_entity_set_tag", "gwaoi_entity_set_tag_batch",
+    "gwaoi_nearest_batch", "gwaoi_nearest_batch_device",
 ]
 
 # every function include/gwaoi_wire.h declares
@@ -86,6 +88,7 @@ DESTROY_REC = 32   # ClientID[16] + EntityID[16]
 SIF_OWN_CLIENT, SIF_NEIGHBOR_CLIENTS = 1, 2
 CAST_REC = 32      # ClientID[16] + msg, src slot, dst slot, 0 (uint32 little-endian): gwaoi_collect_broadcast
 CAST_OWN, CAST_NEIGHBORS = 1, 2
+NO_SLOT = 0xFFFFFFFF  # gwaoi_nearest_batch: no neighbour passes the filter (GWAOI_NO_SLOT)
 CAST_DTYPE = np.dtype([("cid", np.uint8, (16,)), ("msg", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("pad", "<u4")])
 
 
@@ -113,6 +116,10 @@ class StripsConfig(C.Structure):
 class GateRecords(C.Structure):
     _fields_ = [("n_gates", C.c_uint32), ("gate_ids", C.POINTER(C.c_uint16)),
                 ("offsets", C.POINTER(C.c_uint64)), ("records", C.c_void_p)]
+
+
+class SlotRows(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("offsets", C.c_void_p), ("items", C.c_void_p)]
 
 
 class WireGroups(C.Structure):
@@ -236,6 +243,14 @@ def load():
         "gwaoi_collect_broadcast": ([vp, vp, vp, sz, P(GateRecords)], C.c_int),
         "gwaoi_collect_broadcast_device": ([vp, vp, vp, sz, P(GateRecords)], C.c_int),
         "gwaoi_collect_client_switch": ([vp, vp, vp, vp, sz, P(GateRecords), P(GateRecords)], C.c_int),
+        "gwaoi_neighbors_batch": ([vp, vp, sz, P(SlotRows)], C.c_int),
+        "gwaoi_neighbors_batch_device": ([vp, vp, sz, P(SlotRows)], C.c_int),
+        "gwaoi_related_batch": ([vp, vp, vp, sz, vp], C.c_int),
+        "gwaoi_related_batch_device": ([vp, vp, vp, sz, vp], C.c_int),
+        "gwaoi_entity_set_tag": ([vp, u32, u32], C.c_int),
+        "gwaoi_entity_set_tag_batch": ([vp, vp, vp, sz], C.c_int),
+        "gwaoi_nearest_batch": ([vp, vp, vp, vp, sz, vp, vp], C.c_int),
+        "gwaoi_nearest_batch_device": ([vp, vp, vp, vp, sz, vp, vp], C.c_int),
         "gwaoi_wire_create": ([C.c_int, P(vp)], C.c_int),
         "gwaoi_wire_destroy": ([vp], None),
         "gwaoi_wire_last_error": ([vp], C.c_char_p),
@@ -709,6 +724,95 @@ class World:
                                                         C.byref(c), C.byref(d)))
         return ({k: a for k, a in _gate_dict(c, SYNC_OUT_REC).items() if len(a)},
                 {k: a for k, a in _gate_dict(d, DESTROY_REC).items() if len(a)})
+
+    # ---- interest-set reads (include/gwaoi_sync.h)
+    NO_SLOT = NO_SLOT
+
+    def neighbors_batch(self, slots):
+        """InterestedIn of every slots[m] on the relation of the last flush (gwaoi_neighbors_batch):
+        (offsets[n + 1], items) uint32 copies, row m = items[offsets[m]:offsets[m + 1]] in an
+        unspecified order.  A slot outside every AOI space gives an empty row."""
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.uint32).reshape(-1)
+        r = SlotRows()
+        self._check(self._L.gwaoi_neighbors_batch(self._w, _p(s) if s.size else None, s.size, C.byref(r)))
+        off = np.ctypeslib.as_array(C.cast(r.offsets, C.POINTER(C.c_uint32)), shape=(r.n + 1,)).copy()
+        items = (np.ctypeslib.as_array(C.cast(r.items, C.POINTER(C.c_uint32)), shape=(int(off[-1]),)).copy()
+                 if off[-1] else np.empty(0, np.uint32))
+        return off, items
+
+    def neighbors_batch_device(self, d_slots: int, n: int):
+        """Slots in device memory, rows stay in HBM: (offsets pointer, items pointer, n_items), valid
+        until the next rows call.  n_items is offsets[n], read back from the device."""
+        r = SlotRows()
+        self._check(self._L.gwaoi_neighbors_batch_device(self._w, C.c_void_p(d_slots) if d_slots else None, n,
+                                                         C.byref(r)))
+        return r.offsets or 0, r.items or 0, _device_u32((r.offsets or 0) + 4 * r.n)
+
+    def related_batch(self, a, b) -> np.ndarray:
+        """a[m].IsInterestedIn(b[m]) on the relation of the last flush (gwaoi_related_batch): a bool array."""
+        qa = np.ascontiguousarray(np.atleast_1d(a), np.uint32).reshape(-1)
+        qb = np.ascontiguousarray(np.atleast_1d(b), np.uint32).reshape(-1)
+        if qa.size != qb.size:
+            raise ValueError(f"{qa.size} slots a but {qb.size} slots b")
+        out = np.zeros(qa.size, np.uint8)
+        self._check(self._L.gwaoi_related_batch(self._w, _p(qa) if qa.size else None, _p(qb) if qa.size else None,
+                                                qa.size, _p(out) if qa.size else None))
+        return out.astype(bool)
+
+    def related_batch_device(self, d_a: int, d_b: int, n: int, d_out: int):
+        """Pairs and the n answer bytes in device memory."""
+        self._check(self._L.gwaoi_related_batch_device(self._w, C.c_void_p(d_a) if d_a else None,
+                                                       C.c_void_p(d_b) if d_b else None, n,
+                                                       C.c_void_p(d_out) if d_out else None))
+
+    def entity_set_tag(self, slots, tags):
+        """32 caller-defined bits per slot, read by nearest_batch's filter (gwaoi_entity_set_tag_batch)."""
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.uint32).reshape(-1)
+        t = np.ascontiguousarray(np.atleast_1d(tags), np.uint32).reshape(-1)
+        if s.size != t.size:
+            raise ValueError(f"{s.size} slots but {t.size} tags")
+        self._check(self._L.gwaoi_entity_set_tag_batch(self._w, _p(s) if s.size else None, _p(t) if s.size else None,
+                                                       s.size))
+
+    def nearest_batch(self, slots, masks=None, wants=None):
+        """For every slots[m], the neighbour b with (tag[b] & masks[m]) == wants[m] of the smallest
+        DistanceTo, ties to the smallest slot (gwaoi_nearest_batch): (slots uint32, distances
+        float32); NO_SLOT and +inf where there is none.  masks=None: every neighbour."""
+        s = np.ascontiguousarray(np.atleast_1d(slots), np.uint32).reshape(-1)
+        mk = wt = None
+        if masks is not None:
+            mk = np.ascontiguousarray(np.atleast_1d(masks), np.uint32).reshape(-1)
+            wt = np.ascontiguousarray(np.atleast_1d(wants), np.uint32).reshape(-1)
+            if mk.size != s.size or wt.size != s.size:
+                raise ValueError(f"{s.size} slots but {mk.size} masks and {wt.size} wants")
+        out_s, out_d = np.empty(s.size, np.uint32), np.empty(s.size, np.float32)
+        some = s.size > 0
+        self._check(self._L.gwaoi_nearest_batch(self._w, _p(s) if some else None, _p(mk) if some and mk is not None else None,
+                                                _p(wt) if some and wt is not None else None, s.size,
+                                                _p(out_s) if some else None, _p(out_d) if some else None))
+        return out_s, out_d
+
+    def nearest_batch_device(self, d_slots: int, d_masks: int, d_wants: int, n: int, d_out_slot: int, d_out_dist: int):
+        """Every array in device memory (d_masks 0: every neighbour)."""
+        q = [C.c_void_p(p) if p else None for p in (d_slots, d_masks, d_wants)]
+        self._check(self._L.gwaoi_nearest_batch_device(self._w, q[0], q[1], q[2], n,
+                                                       C.c_void_p(d_out_slot) if d_out_slot else None,
+                                                       C.c_void_p(d_out_dist) if d_out_dist else None))
+
+
+_hip = None
+
+
+def _device_u32(ptr: int) -> int:
+    """One uint32 of device memory, through the HIP runtime this process already loaded."""
+    global _hip
+    if _hip is None:
+        _hip = C.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64.so" in line))
+    v = C.c_uint32()
+    rc = _hip.hipMemcpy(C.byref(v), C.c_void_p(ptr), C.c_size_t(4), 2)  # hipMemcpyDeviceToHost
+    if rc != 0:
+        raise GwaoiError(-5, f"hipMemcpy: {rc}")
+    return v.value
 
 
 def _ids(ids, n) -> np.ndarray:

@@ -418,6 +418,11 @@ struct WorldView {
 };
 WorldView world_view(gwaoi_world *w);
 SyncState *&world_sync(gwaoi_world *w);
+// Buffers of the interest-set reads (gwaoi_sync.hip): the world's own, apart from the sync layer,
+// because the rows and membership reads must not create one.
+struct QueryState;
+QueryState *&world_query(gwaoi_world *w);
+void query_destroy(QueryState *q);
 void world_set_error(gwaoi_world *w, const char *msg);
 // Queue a device Moved batch whose ops carry their space (a decoded position
 // packet): op i moves d_slots[i] in space d_sp[i]; SLOT_NONE ops are no-ops.

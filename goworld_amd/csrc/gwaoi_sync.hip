@@ -20,6 +20,11 @@
 //             (slot, new client) message; a destroy record for the old client and a create
 //             record for the new one per B with rel(source, B), grouped by gate; then the
 //             clients are switched.
+// and the interest-set reads of game logic (loops over InterestedIn, Entity.IsInterestedIn,
+// Entity.DistanceTo: Monster.go:49-91, Entity.go:248-256), which deliver nothing and change nothing:
+//   rows      one wave per query slot over the broadcast's window walk; count pass, scan, write pass.
+//   related   one lane per (a, b) pair: two rank lookups, two frame records, one rel().
+//   nearest   one wave per query: the neighbour passing a tag filter with the smallest (d2, slot).
 // Grouping by gate is a multisplit: a first pass counts records per
 // (gate, block) in LDS, an exclusive scan gives every (gate, block) its
 // base, a second pass writes each block's runs (the fan-out's first pass
@@ -1170,6 +1175,210 @@ __global__ void k_switch_apply(const uint4 *__restrict__ m_cid, const uint32_t *
     reinterpret_cast<uint32_t *>(slots)[SLOT_W * (size_t)s + SST_GATE] = g;
 }
 
+// ------------------------------------------------- interest-set reads ------
+// InterestedIn as game logic reads it (Monster.AI's loop, Monster.go:49-65; Entity.IsInterestedIn,
+// Entity.go:248-251; Avatar.go:281-307's count by type), for a batch of queries on the relation
+// of the last flush: the rows themselves (k_rows_*), membership of a pair (k_related) and the
+// nearest neighbour that passes a tag filter (k_nearest).  The rows and the nearest are the
+// broadcast's shape: one wave per query, a block a contiguous chunk, its waves every fourth one,
+// the source's window walked by window_walk; only hits load the candidate's slot (and tag and y),
+// the other lanes re-read the source's through a clamped index.  Nothing takes an atomic per hit:
+// a row's length is a popcount kept in a register, a hit's position the row's base plus the
+// running count plus its rank among the step's hits, so a row's order is that of the walk.
+constexpr unsigned long long Q_E_SLOT = 1ull << 62;  // device forms: a query's slot >= max_slots
+constexpr unsigned long long Q_TOTAL = Q_E_SLOT - 1ull;
+constexpr uint32_t POS_Y = 4 + 1;  // word of y in a slot record (pos = its second uint4)
+
+// The values of loads that every lane issues and only hits use: pinned here, so that the compiler
+// cannot sink a step's loads under that step's hit branch (slot_info's idiom, gwaoi_kernels.hip).
+template <class T>
+__device__ __forceinline__ void keep_loads(T (&v)[CAST_WU]) {
+    static_assert(CAST_WU == 2 && sizeof(T) == 4, "two 32-bit values");
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]));
+}
+
+struct RowsArgs {
+    FrameView F;
+    SlotTab info;
+    const uint32_t *q_slot;  // the queries' slots
+    uint32_t n, max_slots;
+    uint32_t per;            // queries per block
+    uint32_t *cnt;           // n + 1: count pass: row lengths (cnt[n] = 0); scanned in place: the rows' offsets
+    unsigned long long *sc;  // items of all rows (64-bit: the scan's total wraps) | Q_E_SLOT
+    uint32_t *items;         // write pass
+    unsigned long long cap;  // items it holds (the write pass writes nothing past a larger total)
+};
+
+template <bool WRITE>
+__device__ __forceinline__ void rows_pass(const RowsArgs &A) {
+    __shared__ unsigned long long s_tot;
+    // queued behind the count pass and the scan (as cast_pass: the host regrows and relaunches)
+    if (WRITE && (*A.sc & Q_TOTAL) > A.cap) return;
+    const uint32_t blk = blockIdx.x, w = threadIdx.x / 64, ln = s_lane();
+    if (!WRITE) {
+        if (threadIdx.x == 0) s_tot = 0ull;
+        __syncthreads();
+    }
+    const unsigned long long lt = (1ull << ln) - 1ull;
+    unsigned long long wtot = 0ull, werr = 0ull;  // (wave-uniform)
+    const uint32_t m1 = min(A.n, (blk + 1u) * A.per);
+    for (uint32_t m = blk * A.per + w; m < m1; m += ST / 64) {
+        const uint32_t slot = rfl(A.q_slot[m]);
+        const uint32_t base = WRITE ? rfl(A.cnt[m]) : 0u;
+        uint32_t run = 0;  // hits so far (wave-uniform)
+        const bool ok = slot < A.max_slots;  // (device form only: the host form is checked on the host)
+        if (!ok) werr |= Q_E_SLOT;
+        const uint32_t r0 = ok ? rfl(A.info.rank[slot]) : 0xFFFFFFFFu;  // (rank: 0xFFFFFFFF if never live)
+        if (r0 < A.F.n) {
+            const SlotSp S0 = ld_ss(A.F.ss, r0);
+            const Rec16 R = ld_rec(A.F.rec, r0);
+            if (rfl(S0.slot) == slot)  // (else it left the frame: nilSpace or a space without AOI, an empty row)
+                window_walk(A.F, r0, R, S0, w, ln, [&](const uint32_t(&b)[CAST_WU], const uint4(&)[CAST_WU], const bool(&hit)[CAST_WU]) {
+                    if (!WRITE) {
+#pragma unroll
+                        for (int u = 0; u < CAST_WU; ++u) run += (uint32_t)__popcll(__ballot(hit[u]));
+                        return;
+                    }
+                    uint32_t ds[CAST_WU], p[CAST_WU];
+#pragma unroll
+                    for (int u = 0; u < CAST_WU; ++u) ds[u] = ld_ss(A.F.ss, hit[u] ? b[u] : r0).slot;
+                    keep_loads(ds);  // (else the later step's load sinks under its hit branch: a round trip each)
+#pragma unroll
+                    for (int u = 0; u < CAST_WU; ++u) {
+                        const unsigned long long hb = __ballot(hit[u]);
+                        p[u] = base + run + (uint32_t)__popcll(hb & lt);
+                        run += (uint32_t)__popcll(hb);
+                    }
+#pragma unroll
+                    for (int u = 0; u < CAST_WU; ++u)
+                        if (hit[u] && p[u] < A.cap) A.items[p[u]] = ds[u];
+                });
+        }
+        if (!WRITE) {
+            if (ln == 0) A.cnt[m] = run;  // once per query
+            wtot += run;
+        }
+    }
+    if (WRITE) return;
+    if (ln == 0 && wtot) atomicAdd(&s_tot, wtot);
+    if (ln == 0 && werr) atomicOr(A.sc, werr);  // (one lane per wave that saw a bad query)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_tot) atomicAdd(A.sc, s_tot);  // one per block
+        if (blk == 0) A.cnt[A.n] = 0u;      // the scan's last entry becomes the (32-bit) total
+    }
+}
+
+__global__ __launch_bounds__(ST) void k_rows_count(RowsArgs A) { rows_pass<false>(A); }
+__global__ __launch_bounds__(ST) void k_rows_write(RowsArgs A) { rows_pass<true>(A); }
+
+// a[m].IsInterestedIn(b[m]): one lane per pair, two rank lookups and two frame records through
+// clamped indices, no window walk.
+struct RelatedArgs {
+    FrameView F;
+    SlotTab info;
+    const uint32_t *qa, *qb;
+    uint32_t n, max_slots;
+    unsigned long long *sc;  // Q_E_SLOT
+    uint8_t *out;
+};
+
+__global__ __launch_bounds__(ST) void k_related(RelatedArgs A) {
+    const uint32_t i = blockIdx.x * ST + threadIdx.x;
+    const uint32_t m = min(i, A.n - 1u);
+    const uint32_t a = A.qa[m], b = A.qb[m];
+    const bool bad = a >= A.max_slots || b >= A.max_slots;
+    const uint32_t ra = A.info.rank[min(a, A.max_slots - 1u)], rb = A.info.rank[min(b, A.max_slots - 1u)];
+    bool r = false;
+    if (A.F.n) {  // (uniform: an empty frame has no entry 0 to clamp to)
+        const uint32_t ia = ra < A.F.n ? ra : 0u, ib = rb < A.F.n ? rb : 0u;
+        const SlotSp Sa = ld_ss(A.F.ss, ia), Sb = ld_ss(A.F.ss, ib);
+        const Rec16 Ra = ld_rec(A.F.rec, ia), Rb = ld_rec(A.F.rec, ib);
+        const float D = A.F.grid[Sa.sp].D;  // (a frame entry's space: valid whether or not it is a's)
+        const bool in = !bad && ra < A.F.n && rb < A.F.n && Sa.slot == a && Sb.slot == b && Sa.sp == Sb.sp && a != b;
+        r = in && rel(Ra.x, Ra.z, Ra.s, Rb.x, Rb.z, Rb.s, D);
+    }
+    if (i < A.n) {
+        A.out[i] = r ? 1 : 0;
+        if (bad) atomicOr(A.sc, Q_E_SLOT);  // (device form only)
+    }
+}
+
+// The neighbour b of each query's source with (tag[b] & mask) == want and the smallest
+// (squared distance, slot): one wave per query, the rows' walk.  A hit loads its slot, then its
+// tag and y; each lane keeps the smallest key (d2 bits << 32) | slot (d2 >= 0: its bits order as
+// unsigned), a wave min-reduction combines them and lane 0 stores the query's 8 B.
+struct NearArgs {
+    FrameView F;
+    SlotTab info;
+    const uint4 *slots;   // SLOT_U4 per slot (y)
+    const uint32_t *tag;  // per slot
+    const uint32_t *q_slot, *q_mask, *q_want;  // (q_mask nullptr: every neighbour passes)
+    uint32_t n, max_slots;
+    uint32_t per;  // queries per block
+    unsigned long long *sc;  // Q_E_SLOT
+    uint32_t *out_slot;
+    float *out_dist;
+};
+
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o);
+        v = min(v, ((unsigned long long)hi << 32) | lo);
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(ST) void k_nearest(NearArgs A) {
+    const uint32_t blk = blockIdx.x, w = threadIdx.x / 64, ln = s_lane();
+    const float *sw = reinterpret_cast<const float *>(A.slots);
+    unsigned long long werr = 0ull;  // (wave-uniform)
+    const uint32_t m1 = min(A.n, (blk + 1u) * A.per);
+    for (uint32_t m = blk * A.per + w; m < m1; m += ST / 64) {
+        const uint32_t slot = rfl(A.q_slot[m]);
+        const uint32_t mask = A.q_mask ? rfl(A.q_mask[m]) : 0u, want = A.q_mask ? rfl(A.q_want[m]) : 0u;
+        unsigned long long best = ~0ull;
+        const bool ok = slot < A.max_slots;
+        if (!ok) werr |= Q_E_SLOT;
+        const uint32_t r0 = ok ? rfl(A.info.rank[slot]) : 0xFFFFFFFFu;
+        if (r0 < A.F.n) {
+            const SlotSp S0 = ld_ss(A.F.ss, r0);
+            const Rec16 R = ld_rec(A.F.rec, r0);
+            const float y0 = sw[SLOT_W * (size_t)slot + POS_Y];
+            if (rfl(S0.slot) == slot)
+                window_walk(A.F, r0, R, S0, w, ln, [&](const uint32_t(&b)[CAST_WU], const uint4(&q)[CAST_WU], const bool(&hit)[CAST_WU]) {
+                    uint32_t ds[CAST_WU], tg[CAST_WU];
+                    float y[CAST_WU];
+#pragma unroll
+                    for (int u = 0; u < CAST_WU; ++u) ds[u] = ld_ss(A.F.ss, hit[u] ? b[u] : r0).slot;
+#pragma unroll
+                    for (int u = 0; u < CAST_WU; ++u) {
+                        tg[u] = A.tag[ds[u]];
+                        y[u] = sw[SLOT_W * (size_t)ds[u] + POS_Y];
+                    }
+                    keep_loads(tg);  // (issued together for both steps, not under the later step's hit branch)
+                    keep_loads(y);
+#pragma unroll
+                    for (int u = 0; u < CAST_WU; ++u) {
+                        // Vector3.DistanceTo's sum (Vector3.go:22-28), float32 step by step (no contraction)
+                        const float dx = __uint_as_float(q[u].x) - R.x, dy = y[u] - y0, dz = __uint_as_float(q[u].y) - R.z;
+                        const float d2 = (dx * dx + dy * dy) + dz * dz;
+                        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | ds[u];
+                        if (hit[u] && (tg[u] & mask) == want) best = min(best, key);
+                    }
+                });
+        }
+        best = wave_min_u64(best);
+        if (ln == 0) {
+            const bool none = best == ~0ull;
+            A.out_slot[m] = none ? GWAOI_NO_SLOT : (uint32_t)best;
+            A.out_dist[m] = none ? __uint_as_float(0x7F800000u) : (float)sqrt((double)__uint_as_float((uint32_t)(best >> 32)));
+        }
+    }
+    if (ln == 0 && werr) atomicOr(A.sc, werr);
+}
+
 // -------------------------------------------------------------- route ------
 struct RouteArgs {
     const uint32_t *ev;  // (a,b) pairs: [enters | leaves]
@@ -1244,6 +1453,7 @@ struct SyncState {
     uint4 *eid = nullptr, *cid = nullptr;
     uint32_t *sst = nullptr;  // gate, space, syncing, flags
     float4 *pos = nullptr;
+    DevBuf<uint32_t> tag;  // 32 caller-defined bits per slot (gwaoi_entity_set_tag): an array of its own
     DevBuf<unsigned long long> cl;  // 2 per slot: Position / yaw last-writer claims
     DevBuf<uint32_t> oflag, oflag_n;  // decode: slots flagged outside every AOI space
     uint32_t oflag_cap = 0;           // entries of oflag (max_slots)
@@ -1316,7 +1526,7 @@ struct SyncState {
 
 namespace {
 
-enum Arr { A_CGATE, A_QSPACE, A_SYNCING, A_SFLAGS, A_HVAL, A_N32 };
+enum Arr { A_CGATE, A_QSPACE, A_SYNCING, A_SFLAGS, A_HVAL, A_TAG, A_N32 };
 enum Arr128 { B_EID, B_CID, B_HKEY, B_N128 };
 
 ArrTable table32(SyncState *S) {
@@ -1328,6 +1538,8 @@ ArrTable table32(SyncState *S) {
     for (int a = A_CGATE; a <= A_SFLAGS; ++a) T.stride[a] = SLOT_W;
     T.p[A_HVAL] = reinterpret_cast<uint32_t *>(S->htab.get());  // index: the slot word of an entry (hval_word)
     T.stride[A_HVAL] = 1;
+    T.p[A_TAG] = S->tag.get();
+    T.stride[A_TAG] = 1;
     return T;
 }
 ArrTable table128(SyncState *S) {
@@ -1422,7 +1634,8 @@ int create(gwaoi_world *w, SyncState **out) {
     S->hcap = cap;
     const size_t N = v.max_slots;
     S->oflag_cap = (uint32_t)N;
-    if (int rc = alloc_all(w, S->slots, SLOT_U4 * N, S->cl, 2 * N, S->oflag, N, S->oflag_n, 1, S->htab, 4 * (size_t)nbk)) {
+    if (int rc = alloc_all(w, S->slots, SLOT_U4 * N, S->cl, 2 * N, S->oflag, N, S->oflag_n, 1, S->htab, 4 * (size_t)nbk,
+                       S->tag, N)) {
         sync_destroy(S);
         return rc;
     }
@@ -1432,6 +1645,7 @@ int create(gwaoi_world *w, SyncState **out) {
     S->cid = S->slots + 3;
     bool ok = hipMemsetAsync(S->slots, 0, N * 16 * SLOT_U4, S->st) == hipSuccess &&
               hipMemsetAsync(S->cl, 0, N * 16, S->st) == hipSuccess &&
+              hipMemsetAsync(S->tag, 0, N * 4, S->st) == hipSuccess &&
               hipMemsetAsync(S->oflag_n, 0, 4, S->st) == hipSuccess &&
               hipMemsetAsync(S->htab, 0xFF, (size_t)nbk * 64, S->st) == hipSuccess &&  // every entry H_EMPTY
               S->stage_ev.create(hipEventDisableTiming) == GWAOI_OK && S->ndec_ev.create(hipEventDisableTiming) == GWAOI_OK &&
@@ -2074,6 +2288,257 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
 
 }  // namespace
 
+// Buffers of the interest-set reads.  The world's own (world_query), apart from SyncState: the
+// rows and membership reads need no sync layer and must not create one.
+struct QueryState {
+    DevBuf<uint32_t> in;             // the host forms' uploaded queries
+    DevBuf<uint32_t> cnt, scan_tmp;  // rows: n + 1 lengths, scanned in place into the offsets
+    DevBuf<uint32_t> items;          // rows: neighbour slots (valid until the next rows call)
+    DevBuf<unsigned long long> sc;   // 64-bit total | Q_E_SLOT
+    PinnedBuf<unsigned long long> h_sc;
+    PinnedBuf<uint32_t> h_off, h_items;  // the host form's rows
+    DevBuf<uint32_t> out;            // the host forms' membership / nearest answers on the device
+};
+
+void query_destroy(QueryState *Q) { delete Q; }  // (the world has synchronised its streams)
+
+namespace {
+
+int query_state(gwaoi_world *w, QueryState **out) {
+    QueryState *&Q = world_query(w);
+    if (!Q) {
+        Q = new (std::nothrow) QueryState();
+        if (!Q) return GWAOI_ENOMEM;
+    }
+    if (!Q->sc)
+        if (int rc = alloc_all(w, Q->sc, 1)) return rc;
+    if (!Q->h_sc)
+        if (int rc = alloc_pinned(w, Q->h_sc, 1)) return rc;
+    *out = Q;
+    return GWAOI_OK;
+}
+
+template <class T>
+int q_ensure(gwaoi_world *w, DevBuf<T> &b, size_t n) {
+    if (n <= b.cap()) return GWAOI_OK;
+    return alloc_all(w, b, std::max<size_t>(n + n / 4, 1024));
+}
+int q_ensure_host(gwaoi_world *w, PinnedBuf<uint32_t> &b, size_t n) {
+    if (n <= b.cap()) return GWAOI_OK;
+    return alloc_pinned(w, b, std::max<size_t>(n + n / 8, 1 << 14));
+}
+
+// one wave per query: a block loops over a contiguous chunk, its waves every (ST / 64)-th one,
+// and the grid is capped as the broadcast's
+uint32_t query_chunk(size_t n) {
+    return std::max<uint32_t>(ST / 64, (cdivu(n, CAST_MAX_BLOCKS) + ST / 64 - 1) / (ST / 64) * (ST / 64));
+}
+
+// the total | error word to the host: the call's host wait
+int query_sc(gwaoi_world *w, QueryState *Q, hipStream_t st, unsigned long long *sc) {
+    HIP_TRY(w, hipMemcpyAsync(Q->h_sc, Q->sc, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(w, hipStreamSynchronize(st));
+    *sc = *Q->h_sc;
+    return GWAOI_OK;
+}
+
+// gwaoi_neighbors_batch(_device): reads only the frame.
+int query_rows(gwaoi_world *w, const uint32_t *slots, size_t n, gwaoi_slot_rows *out, bool on_device) {
+    if (!w || !out || (n && !slots)) return GWAOI_EINVAL;
+    const WorldView v = world_view(w);
+    if (v.pending_ops) return GWAOI_ESTATE;
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    if (!on_device)  // nothing is produced on error: checked before any device work
+        for (size_t m = 0; m < n; ++m)
+            if (slots[m] >= v.max_slots) return GWAOI_EBADSLOT;
+    QueryState *Q;
+    if (int rc = query_state(w, &Q)) return rc;
+    if (int rc = q_ensure(w, Q->cnt, n + 1)) return rc;
+    if (int rc = q_ensure(w, Q->items, 1)) return rc;  // (an empty result's pointer)
+    uint64_t total = 0;
+    int status = GWAOI_OK;
+    if (n) {
+        RowsArgs A{};
+        A.F = v.F;
+        A.info = v.info;
+        if (on_device) {
+            A.q_slot = slots;
+        } else {
+            if (int rc = q_ensure(w, Q->in, n)) return rc;
+            HIP_TRY(w, hipMemcpyAsync(Q->in, slots, n * 4, hipMemcpyHostToDevice, v.st));
+            A.q_slot = Q->in;
+        }
+        A.n = (uint32_t)n;
+        A.max_slots = v.max_slots;
+        A.per = query_chunk(n);
+        const uint32_t nb = cdivu(n, A.per);
+        A.cnt = Q->cnt;
+        A.sc = Q->sc;
+        if (int rc = q_ensure(w, Q->scan_tmp, scan_tmp_elems(n + 1) + 4)) return rc;
+        HIP_TRY(w, hipMemsetAsync(Q->sc, 0, 8, v.st));
+        k_rows_count<<<nb, ST, 0, v.st>>>(A);
+        HIP_TRY(w, hipGetLastError());
+        scan_exclusive(Q->cnt, Q->cnt, n + 1, Q->scan_tmp, v.st);
+        // the write pass is queued with the items as they are (the last call's size) before the one
+        // host wait, which brings the 64-bit total and the device form's error bit
+        A.items = Q->items;
+        A.cap = Q->items.cap();
+        k_rows_write<<<nb, ST, 0, v.st>>>(A);
+        HIP_TRY(w, hipGetLastError());
+        unsigned long long sc;
+        if (int rc = query_sc(w, Q, v.st, &sc)) return rc;
+        if (sc & Q_E_SLOT) status = GWAOI_EBADSLOT;
+        total = sc & Q_TOTAL;
+        if (total > 0xFFFFFFFFull) {
+            world_set_error(w, "query: rows of more than 2^32 - 1 items");
+            return GWAOI_ECAPACITY;
+        }
+        if (total > A.cap) {  // (the write pass declined: more items than the output holds)
+            if (int rc = q_ensure(w, Q->items, total)) return rc;
+            A.items = Q->items;
+            A.cap = Q->items.cap();
+            k_rows_write<<<nb, ST, 0, v.st>>>(A);
+            HIP_TRY(w, hipGetLastError());
+            if (on_device) HIP_TRY(w, hipStreamSynchronize(v.st));  // (the rows are complete on return)
+        }
+    } else {
+        HIP_TRY(w, hipMemsetAsync(Q->cnt, 0, 4, v.st));
+        if (on_device) HIP_TRY(w, hipStreamSynchronize(v.st));
+    }
+    out->n = (uint32_t)n;
+    if (on_device) {
+        out->offsets = Q->cnt;
+        out->items = Q->items;
+    } else {
+        if (int rc = q_ensure_host(w, Q->h_off, n + 1)) return rc;
+        if (int rc = q_ensure_host(w, Q->h_items, std::max<uint64_t>(total, 1))) return rc;
+        HIP_TRY(w, hipMemcpyAsync(Q->h_off, Q->cnt, (n + 1) * 4, hipMemcpyDeviceToHost, v.st));
+        if (total) HIP_TRY(w, hipMemcpyAsync(Q->h_items, Q->items, total * 4, hipMemcpyDeviceToHost, v.st));
+        HIP_TRY(w, hipStreamSynchronize(v.st));
+        out->offsets = Q->h_off;
+        out->items = Q->h_items;
+    }
+    if (status != GWAOI_OK) world_set_error(w, "query: rows of a slot >= max_slots are empty");
+    return status;
+}
+
+// gwaoi_related_batch(_device): reads only the frame.
+int query_related(gwaoi_world *w, const uint32_t *a, const uint32_t *b, size_t n, uint8_t *out, bool on_device) {
+    if (!w || (n && (!a || !b || !out))) return GWAOI_EINVAL;
+    const WorldView v = world_view(w);
+    if (v.pending_ops) return GWAOI_ESTATE;
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    if (!on_device)
+        for (size_t m = 0; m < n; ++m)
+            if (a[m] >= v.max_slots || b[m] >= v.max_slots) return GWAOI_EBADSLOT;
+    if (!n) return GWAOI_OK;
+    QueryState *Q;
+    if (int rc = query_state(w, &Q)) return rc;
+    RelatedArgs A{};
+    A.F = v.F;
+    A.info = v.info;
+    if (on_device) {
+        A.qa = a;
+        A.qb = b;
+        A.out = out;
+    } else {
+        if (int rc = q_ensure(w, Q->in, 2 * n)) return rc;
+        if (int rc = q_ensure(w, Q->out, n / 4 + 1)) return rc;
+        HIP_TRY(w, hipMemcpyAsync(Q->in, a, n * 4, hipMemcpyHostToDevice, v.st));
+        HIP_TRY(w, hipMemcpyAsync(Q->in + n, b, n * 4, hipMemcpyHostToDevice, v.st));
+        A.qa = Q->in;
+        A.qb = Q->in + n;
+        A.out = reinterpret_cast<uint8_t *>(Q->out.get());
+    }
+    A.n = (uint32_t)n;
+    A.max_slots = v.max_slots;
+    A.sc = Q->sc;
+    HIP_TRY(w, hipMemsetAsync(Q->sc, 0, 8, v.st));
+    k_related<<<cdivu(n, ST), ST, 0, v.st>>>(A);
+    HIP_TRY(w, hipGetLastError());
+    if (!on_device) HIP_TRY(w, hipMemcpyAsync(out, A.out, n, hipMemcpyDeviceToHost, v.st));
+    unsigned long long sc;
+    if (int rc = query_sc(w, Q, v.st, &sc)) return rc;
+    if (sc & Q_E_SLOT) {
+        world_set_error(w, "query: pairs with a slot >= max_slots are not related");
+        return GWAOI_EBADSLOT;
+    }
+    return GWAOI_OK;
+}
+
+// gwaoi_nearest_batch(_device): the frame, the tags and the slots' y (the sync layer's).
+int query_nearest(gwaoi_world *w, const uint32_t *slots, const uint32_t *masks, const uint32_t *wants, size_t n,
+                  uint32_t *out_slot, float *out_dist, bool on_device) {
+    if (!w || (n && (!slots || !out_slot || !out_dist || (masks && !wants)))) return GWAOI_EINVAL;
+    SyncState *S;
+    if (int rc = state(w, &S)) return rc;
+    const WorldView v = world_view(w);
+    if (v.pending_ops) return GWAOI_ESTATE;
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    if (!on_device)
+        for (size_t m = 0; m < n; ++m)
+            if (slots[m] >= v.max_slots) return GWAOI_EBADSLOT;
+    if (!n) return GWAOI_OK;
+    QueryState *Q;
+    if (int rc = query_state(w, &Q)) return rc;
+    if (int rc = push(S)) return rc;  // every earlier tag and position write is visible
+    NearArgs A{};
+    A.F = v.F;
+    A.info = v.info;
+    A.slots = S->slots;
+    A.tag = S->tag;
+    if (on_device) {
+        A.q_slot = slots;
+        A.q_mask = masks;
+        A.q_want = masks ? wants : nullptr;
+        A.out_slot = out_slot;
+        A.out_dist = out_dist;
+    } else {
+        if (int rc = q_ensure(w, Q->in, 3 * n)) return rc;
+        if (int rc = q_ensure(w, Q->out, 2 * n)) return rc;
+        HIP_TRY(w, hipMemcpyAsync(Q->in, slots, n * 4, hipMemcpyHostToDevice, v.st));
+        if (masks) {
+            HIP_TRY(w, hipMemcpyAsync(Q->in + n, masks, n * 4, hipMemcpyHostToDevice, v.st));
+            HIP_TRY(w, hipMemcpyAsync(Q->in + 2 * n, wants, n * 4, hipMemcpyHostToDevice, v.st));
+        }
+        A.q_slot = Q->in;
+        A.q_mask = masks ? Q->in + n : nullptr;
+        A.q_want = masks ? Q->in + 2 * n : nullptr;
+        A.out_slot = Q->out;
+        A.out_dist = reinterpret_cast<float *>(Q->out + n);
+    }
+    A.n = (uint32_t)n;
+    A.max_slots = v.max_slots;
+    A.per = query_chunk(n);
+    A.sc = Q->sc;
+    HIP_TRY(w, hipMemsetAsync(Q->sc, 0, 8, v.st));
+    k_nearest<<<cdivu(n, A.per), ST, 0, v.st>>>(A);
+    HIP_TRY(w, hipGetLastError());
+    if (!on_device) {
+        HIP_TRY(w, hipMemcpyAsync(out_slot, A.out_slot, n * 4, hipMemcpyDeviceToHost, v.st));
+        HIP_TRY(w, hipMemcpyAsync(out_dist, A.out_dist, n * 4, hipMemcpyDeviceToHost, v.st));
+    }
+    unsigned long long sc;
+    if (int rc = query_sc(w, Q, v.st, &sc)) return rc;
+    if (sc & Q_E_SLOT) {
+        world_set_error(w, "query: sources with a slot >= max_slots have no nearest neighbour");
+        return GWAOI_EBADSLOT;
+    }
+    return GWAOI_OK;
+}
+
+int set_tags(gwaoi_world *w, const uint32_t *slots, const uint32_t *tags, size_t n) {
+    if (!w || (n && (!slots || !tags))) return GWAOI_EINVAL;
+    SyncState *S;
+    if (int rc = state(w, &S)) return rc;
+    for (size_t i = 0; i < n; ++i)
+        if (slots[i] >= S->max_slots) return GWAOI_EBADSLOT;
+    for (size_t i = 0; i < n; ++i) put32(S, A_TAG, slots[i], tags[i]);  // (push keeps a slot's last write)
+    return GWAOI_OK;
+}
+
+}  // namespace
+
 void sync_note_slot(SyncState *S, uint32_t slot, uint32_t space_or_dead) {
     put32(S, A_QSPACE, slot, space_or_dead);
     if (space_or_dead == SP_DEAD)
@@ -2135,6 +2600,7 @@ int gwaoi_entity_unbind(gwaoi_world *w, uint32_t slot) {
         gw::put32(S, gw::A_CGATE, slot, gw::NO_GATE);
     }
     gw::put32(S, gw::A_SYNCING, slot, 0);
+    gw::put32(S, gw::A_TAG, slot, 0);
     return GWAOI_OK;
     });
 }
@@ -2275,6 +2741,42 @@ int gwaoi_collect_client_switch(gwaoi_world *w, const uint32_t *slots, const uin
                                 gwaoi_gate_records *destroys) {
     return gw::api_guard([&]() -> int {
     return gw::collect_switch(w, slots, gate_ids, clientids, n, creates, destroys);
+    });
+}
+
+int gwaoi_neighbors_batch(gwaoi_world *w, const uint32_t *slots, size_t n, gwaoi_slot_rows *out) {
+    return gw::api_guard([&]() -> int { return gw::query_rows(w, slots, n, out, false); });
+}
+
+int gwaoi_neighbors_batch_device(gwaoi_world *w, const uint32_t *d_slots, size_t n, gwaoi_slot_rows *out) {
+    return gw::api_guard([&]() -> int { return gw::query_rows(w, d_slots, n, out, true); });
+}
+
+int gwaoi_related_batch(gwaoi_world *w, const uint32_t *a, const uint32_t *b, size_t n, uint8_t *out) {
+    return gw::api_guard([&]() -> int { return gw::query_related(w, a, b, n, out, false); });
+}
+
+int gwaoi_related_batch_device(gwaoi_world *w, const uint32_t *d_a, const uint32_t *d_b, size_t n, uint8_t *d_out) {
+    return gw::api_guard([&]() -> int { return gw::query_related(w, d_a, d_b, n, d_out, true); });
+}
+
+int gwaoi_entity_set_tag(gwaoi_world *w, uint32_t slot, uint32_t tag) {
+    return gw::api_guard([&]() -> int { return gw::set_tags(w, &slot, &tag, 1); });
+}
+
+int gwaoi_entity_set_tag_batch(gwaoi_world *w, const uint32_t *slots, const uint32_t *tags, size_t n) {
+    return gw::api_guard([&]() -> int { return gw::set_tags(w, slots, tags, n); });
+}
+
+int gwaoi_nearest_batch(gwaoi_world *w, const uint32_t *slots, const uint32_t *masks, const uint32_t *wants,
+                        size_t n, uint32_t *out_slot, float *out_dist) {
+    return gw::api_guard([&]() -> int { return gw::query_nearest(w, slots, masks, wants, n, out_slot, out_dist, false); });
+}
+
+int gwaoi_nearest_batch_device(gwaoi_world *w, const uint32_t *d_slots, const uint32_t *d_masks,
+                               const uint32_t *d_wants, size_t n, uint32_t *d_out_slot, float *d_out_dist) {
+    return gw::api_guard([&]() -> int {
+    return gw::query_nearest(w, d_slots, d_masks, d_wants, n, d_out_slot, d_out_dist, true);
     });
 }
 

@@ -381,6 +381,7 @@ struct gwaoi_world {
     bool poisoned = false;
     std::string poison_msg;
     gw::SyncState *sync = nullptr;  // entity position-sync layer (gwaoi_sync.h), created on first use
+    gw::QueryState *query = nullptr;  // buffers of the interest-set reads (gwaoi_sync.h), created on first use
 };
 
 namespace {
@@ -1533,6 +1534,8 @@ int gwaoi_world_destroy(gwaoi_world *w) {
     if (w->out_st) (void)hipStreamSynchronize(w->out_st);
     if (w->sync) gw::sync_destroy(w->sync);
     w->sync = nullptr;
+    if (w->query) gw::query_destroy(w->query);
+    w->query = nullptr;
     delete w;
     return GWAOI_OK;
     });
@@ -2232,6 +2235,7 @@ WorldView world_view(gwaoi_world *w) {
 }
 
 SyncState *&world_sync(gwaoi_world *w) { return w->sync; }
+QueryState *&world_query(gwaoi_world *w) { return w->query; }
 
 void world_set_error(gwaoi_world *w, const char *msg) { w->last_error = msg; }
 

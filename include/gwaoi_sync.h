@@ -28,6 +28,12 @@
  *   Entity.SetClient                    Entity.go:678-724       gwaoi_collect_client_switch
  *   Entity.GiveClientTo                 Entity.go:752-765         (the create / destroy lists of the
  *                                                                  entities in InterestedBy, and the switch)
+ *   loops over Entity.InterestedIn     examples/unity_demo/Monster.go:49-65 (Monster.AI),
+ *     examples/test_game/Avatar.go:281-307                      gwaoi_neighbors_batch(_device)
+ *   Entity.IsInterestedIn               Entity.go:248-251       gwaoi_related_batch(_device)
+ *     (Monster.Tick, Monster.go:81,91)
+ *   Monster.AI's nearest living Player: Entity.DistanceTo       gwaoi_entity_set_tag(_batch) +
+ *     Entity.go:253-256, Vector3.go:22-28                         gwaoi_nearest_batch(_device)
  *
  * Entity ids and client ids are the reference's 16-byte strings
  * (common.ENTITYID_LENGTH = common.CLIENTID_LENGTH = uuid.UUID_LENGTH = 16,
@@ -239,6 +245,87 @@ int gwaoi_collect_broadcast_device(gwaoi_world *w, const uint32_t *d_slots, cons
 int gwaoi_collect_client_switch(gwaoi_world *w, const uint32_t *slots, const uint16_t *gate_ids,
                                 const uint8_t *clientids /* 16 B per message, NULL: all detach */,
                                 size_t n, gwaoi_gate_records *creates, gwaoi_gate_records *destroys);
+
+/* ---- interest-set reads ---------------------------------------------------- */
+/* InterestedIn / InterestedBy as game logic reads them, for a batch of queries
+ * on the GPU: the rows themselves, membership of a pair, and the nearest
+ * neighbour that passes a tag filter (Monster.AI, Monster.Tick,
+ * Avatar.TestCallAll_Client; see the table at the top).
+ *
+ * Relation.  That of the last committed flush, the one gwaoi_neighbors and the
+ * collects read.  Every call below returns GWAOI_ESTATE with ops queued or a
+ * flush in flight, exactly as the collects do (a decoded sync packet writes Y
+ * and yaw before its flush: a read with ops queued would mix frames).
+ * No side effects.  Nothing here changes sync flags, positions, clients or
+ * the relation; a query made twice gives the same answer.
+ * Outside the frame.  A slot never entered, one that left, one in nilSpace or
+ * in a space without AOI has no neighbours: an empty row, membership 0, no
+ * nearest.  That is not an error (gwaoi_neighbors keeps its GWAOI_ESTATE).
+ * Errors, host forms (nothing is produced): a null world or output, or a null
+ * input array with n > 0: GWAOI_EINVAL; a slot >= max_slots: GWAOI_EBADSLOT.
+ * Errors, device forms (inputs in device memory of the world's GPU, read
+ * before the call returns): a query with a slot >= max_slots gets the
+ * "outside the frame" answer, the other answers are delivered, the call
+ * returns GWAOI_EBADSLOT and the world stays usable (the broadcast's
+ * device-form convention). */
+
+/* Rows of neighbour slots: row m = items[offsets[m] .. offsets[m+1]). */
+typedef struct {
+    uint32_t n;              /* rows = queries                                   */
+    const uint32_t *offsets; /* n + 1 entries; row m = items[offsets[m] .. offsets[m+1]) */
+    const uint32_t *items;   /* neighbour slots                                  */
+} gwaoi_slot_rows;
+
+/* Row m is InterestedIn of slots[m]; as a set that equals InterestedBy:
+ * {b : rel(slots[m], b)}, never the slot itself.  The order within a row is
+ * unspecified, the set is exact.  A slot may repeat: each query gets its own
+ * row.  offsets and items are world-owned host memory, valid until the next
+ * rows call (of either form).  n == 0 gives out->n == 0, a one-entry offsets
+ * and GWAOI_OK; more than 2^32 - 1 items give GWAOI_ECAPACITY.
+ * These two calls and the membership calls read only the frame: they work on
+ * a world on which no other call of this header was ever made, and leave it
+ * so (a strip world stays one that accepts device Enter / Leave batches). */
+int gwaoi_neighbors_batch(gwaoi_world *w, const uint32_t *slots, size_t n, gwaoi_slot_rows *out);
+/* Same; d_slots in device memory, offsets and items both stay in device
+ * memory (offsets[n], the number of items, included), valid until the next
+ * rows call.  One host wait unless the items outgrew the last call's. */
+int gwaoi_neighbors_batch_device(gwaoi_world *w, const uint32_t *d_slots, size_t n, gwaoi_slot_rows *out);
+
+/* out[m] = a[m].IsInterestedIn(b[m]) (Entity.go:248-251): 1 iff both slots are
+ * in the frame, in the same space, distinct, and rel() holds for the pair (the
+ * owner of the window is the later seq, as everywhere); otherwise 0. */
+int gwaoi_related_batch(gwaoi_world *w, const uint32_t *a, const uint32_t *b, size_t n, uint8_t *out);
+/* Same; d_a, d_b and d_out (n bytes) in device memory, complete on return. */
+int gwaoi_related_batch_device(gwaoi_world *w, const uint32_t *d_a, const uint32_t *d_b, size_t n, uint8_t *d_out);
+
+/* A tag: 32 caller-defined bits per slot (for unity_demo: the entity type and
+ * an "hp > 0" bit), 0 by default, kept across Enter / Leave and cleared by
+ * gwaoi_entity_unbind.  Setting one is not an AOI op: it is allowed with ops
+ * queued and visible to every later query, as gwaoi_entity_set_client is to
+ * the collects.  Within one batch the last write of a slot wins.
+ * GWAOI_EBADSLOT for a slot >= max_slots (the batch then sets nothing). */
+int gwaoi_entity_set_tag(gwaoi_world *w, uint32_t slot, uint32_t tag);
+int gwaoi_entity_set_tag_batch(gwaoi_world *w, const uint32_t *slots, const uint32_t *tags, size_t n);
+
+#define GWAOI_NO_SLOT 0xFFFFFFFFu
+/* Monster.AI's search (Monster.go:49-65): among the b in InterestedIn(slots[m])
+ * with (tag[b] & masks[m]) == wants[m], the one with the smallest squared
+ * distance; ties go to the smallest slot.  masks == NULL (wants is then
+ * ignored) means every neighbour.
+ * Distance.  Vector3.DistanceTo on amd64 (Entity.go:253-256, Vector3.go:22-28):
+ * dx = b.x - a.x, likewise dy and dz, d2 = fl32(fl32(fl32(dx*dx) + fl32(dy*dy))
+ * + fl32(dz*dz)) with no fused step, out_dist[m] = (float)sqrt((double)d2).
+ * x and z are the frame's (the AOI position of the last flush), y is the
+ * slot's position record (what the sync records report).  Minimising
+ * (d2, slot) picks an entity of minimal DistanceTo: one of the outcomes the
+ * reference's map-order loop can produce, and the deterministic one.
+ * No candidate (nobody passes the filter, an empty row, a source outside the
+ * frame): out_slot[m] = GWAOI_NO_SLOT and out_dist[m] = +inf. */
+int gwaoi_nearest_batch(gwaoi_world *w, const uint32_t *slots, const uint32_t *masks, const uint32_t *wants,
+                        size_t n, uint32_t *out_slot, float *out_dist);
+/* Same; every array in device memory, the outputs complete on return. */
+int gwaoi_nearest_batch_device(gwaoi_world *w, const uint32_t *d_slots, const uint32_t *d_masks,
+                               const uint32_t *d_wants, size_t n, uint32_t *d_out_slot, float *d_out_dist);
 
 #ifdef __cplusplus
 }
