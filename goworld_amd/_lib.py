@@ -72,7 +72,7 @@ SYNC_EXPORTS = [
     "gwaoi_entity_leave_plain", "gwaoi_collect_broadcast", "gwaoi_collect_broadcast_device",
     "gwaoi_collect_client_switch", "gwaoi_neighbors_batch", "gwaoi_neighbors_batch_device",
     "gwaoi_related_batch", "gwaoi_related_batch_device", "gwaoi_entity_set_tag", "gwaoi_entity_set_tag_batch",
-    "gwaoi_nearest_batch", "gwaoi_nearest_batch_device",
+    "gwaoi_nearest_batch", "gwaoi_nearest_batch_device", "gwaoi_steer_batch", "gwaoi_steer_batch_device",
 ]
 
 # every function include/gwaoi_wire.h declares
@@ -89,6 +89,7 @@ SIF_OWN_CLIENT, SIF_NEIGHBOR_CLIENTS = 1, 2
 CAST_REC = 32      # ClientID[16] + msg, src slot, dst slot, 0 (uint32 little-endian): gwaoi_collect_broadcast
 CAST_OWN, CAST_NEIGHBORS = 1, 2
 NO_SLOT = 0xFFFFFFFF  # gwaoi_nearest_batch: no neighbour passes the filter (GWAOI_NO_SLOT)
+STEER_MOVE, STEER_FACE = 1, 2  # gwaoi_steer_batch flags (GWAOI_STEER_MOVE / GWAOI_STEER_FACE)
 CAST_DTYPE = np.dtype([("cid", np.uint8, (16,)), ("msg", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("pad", "<u4")])
 
 
@@ -145,6 +146,7 @@ class GwaoiError(RuntimeError):
         super().__init__(f"{STATUS.get(code, code)}: {msg}")
         self.code = code
         self.events = None  # tick(): the committed flush's (enter, leave) pairs, still to replay
+        self.result = None  # steer_batch(): (applied, pos) when messages were dropped on the device (overflow)
 
 
 _lib = None
@@ -251,6 +253,8 @@ def load():
         "gwaoi_entity_set_tag_batch": ([vp, vp, vp, sz], C.c_int),
         "gwaoi_nearest_batch": ([vp, vp, vp, vp, sz, vp, vp], C.c_int),
         "gwaoi_nearest_batch_device": ([vp, vp, vp, vp, sz, vp, vp], C.c_int),
+        "gwaoi_steer_batch": ([vp, vp, vp, vp, vp, sz, vp, vp], C.c_int),
+        "gwaoi_steer_batch_device": ([vp, vp, vp, vp, vp, sz, vp, vp], C.c_int),
         "gwaoi_wire_create": ([C.c_int, P(vp)], C.c_int),
         "gwaoi_wire_destroy": ([vp], None),
         "gwaoi_wire_last_error": ([vp], C.c_char_p),
@@ -798,6 +802,45 @@ class World:
         self._check(self._L.gwaoi_nearest_batch_device(self._w, q[0], q[1], q[2], n,
                                                        C.c_void_p(d_out_slot) if d_out_slot else None,
                                                        C.c_void_p(d_out_dist) if d_out_dist else None))
+
+    # ---- server-driven movement (include/gwaoi_sync.h)
+    STEER_MOVE, STEER_FACE = STEER_MOVE, STEER_FACE
+
+    def steer_batch(self, movers, targets, steps, flags=None):
+        """Monster.Tick's chase and FaceTo for a batch (gwaoi_steer_batch): mover m steps steps[m]
+        toward targets[m] (STEER_MOVE) and faces it (STEER_FACE) if it is interested in it on the
+        relation of the last flush; flags=None: both for every message.  Returns (applied bool[n],
+        pos float32[n, 4]: the movers' x, y, z, yaw after their message, zeros where none applied).
+        The moves are queued: tick before the next read or collect.  When the device drops a message
+        whose new position overflows, the GwaoiError raised carries the answers in .result."""
+        mv = np.ascontiguousarray(np.atleast_1d(movers), np.uint32).reshape(-1)
+        tg = np.ascontiguousarray(np.atleast_1d(targets), np.uint32).reshape(-1)
+        st = np.ascontiguousarray(np.atleast_1d(steps), np.float32).reshape(-1)
+        fl = None
+        if flags is not None:
+            fl = np.ascontiguousarray(np.atleast_1d(flags), np.uint32).reshape(-1)
+        if tg.size != mv.size or st.size != mv.size or (fl is not None and fl.size != mv.size):
+            raise ValueError(f"{mv.size} movers but {tg.size} targets, {st.size} steps and "
+                             f"{'no' if fl is None else fl.size} flags")
+        applied, pos = np.zeros(mv.size, np.uint8), np.zeros((mv.size, 4), np.float32)
+        some = mv.size > 0
+        rc = self._L.gwaoi_steer_batch(self._w, _p(mv) if some else None, _p(tg) if some else None,
+                                       _p(st) if some else None, _p(fl) if some and fl is not None else None,
+                                       mv.size, _p(applied) if some else None, _p(pos) if some else None)
+        try:
+            self._check(rc)
+        except GwaoiError as e:
+            e.result = (applied.astype(bool), pos)
+            raise
+        return applied.astype(bool), pos
+
+    def steer_batch_device(self, d_movers: int, d_targets: int, d_steps: int, d_flags: int, n: int,
+                           d_out_applied: int, d_out_pos: int):
+        """Every array in device memory (d_flags 0: MOVE | FACE for every message); d_targets may be
+        nearest_batch_device's output as it is.  The outputs (n bytes, 4n floats) are complete on
+        return, also when a GwaoiError reports dropped messages."""
+        q = [C.c_void_p(p) if p else None for p in (d_movers, d_targets, d_steps, d_flags, d_out_applied, d_out_pos)]
+        self._check(self._L.gwaoi_steer_batch_device(self._w, q[0], q[1], q[2], q[3], n, q[4], q[5]))
 
 
 _hip = None

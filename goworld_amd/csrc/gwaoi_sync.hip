@@ -39,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <unordered_map>
@@ -1379,6 +1380,155 @@ __global__ __launch_bounds__(ST) void k_nearest(NearArgs A) {
     if (ln == 0 && werr) atomicOr(A.sc, werr);
 }
 
+// ------------------------------------------------ server-driven movement ------
+// Monster.Tick's chase and FaceTo (Monster.go:80-102, Entity.go:1292-1304, Vector3.go:44-77) for a
+// batch of (mover, target, step, flags) messages: one lane per message, k_related's gate (two rank
+// lookups, two frame records, one rel()) and then a handful of float32 operations in the reference's
+// order.  Compute-then-apply: k_steer reads the frame and the movers' slot records, which nothing in
+// it writes, and leaves each applied message's result in the outputs, its Moved op in the batch
+// arrays and its claim in cl; k_steer_apply then writes the slot records of the messages whose claim
+// store survived (the decode's claim-store-then-compare: a mover named twice keeps one message).
+constexpr uint32_t STEER_E_SLOT = 1u, STEER_E_INVAL = 2u, STEER_E_NONFINITE = 4u;  // the status word
+constexpr uint32_t STEER_ALL = GWAOI_STEER_MOVE | GWAOI_STEER_FACE;
+
+struct SteerArgs {
+    FrameView F;
+    SlotTab info;
+    const uint4 *slots;  // SLOT_U4 per slot: sst, pos, eid, cid
+    const uint32_t *mv, *tg;
+    const float *step;
+    const uint32_t *flags;  // nullptr: MOVE | FACE for every message
+    uint32_t n, max_slots;
+    uint32_t *o_slot, *o_sp;  // the device Moved batch (SLOT_NONE: no move)
+    float *o_x, *o_z;
+    uint32_t *o_ms;  // mover of an applied message (SLOT_NONE: not applied), for k_steer_apply
+    unsigned long long claim0;
+    unsigned long long *cl;
+    uint32_t *sst;
+    float4 *pos;
+    uint8_t *out_applied;
+    float *out_pos;  // 4 per message: x, y, z, yaw
+    uint32_t *status;  // STEER_E_*
+};
+
+// Vector3.Normalize as written (Vector3.go:64-72): the sum takes Y itself, twice, not its square.
+__device__ __forceinline__ void steer_normalize(float &x, float &y, float &z) {
+    const float sum = ((x * x + y) + y) + z * z;
+    const float d = (float)sqrt((double)sum);
+    if (d == 0.0f) return;
+    x = x / d;
+    y = y / d;
+    z = z / d;
+}
+
+// Vector3.DirToYaw (Vector3.go:45-62) of a direction with Y = 0: float64 throughout, then Yaw(float32).
+__device__ __forceinline__ float steer_dir_to_yaw(float x, float z) {
+    float y = 0.0f;
+    steer_normalize(x, y, z);
+    double yaw = acos((double)x);
+    if (z < 0.0f) yaw = 6.283185307179586 - yaw;
+    yaw = yaw / 3.141592653589793 * 180.0;
+    yaw = yaw <= 90.0 ? 90.0 - yaw : 90.0 + (360.0 - yaw);
+    return (float)yaw;
+}
+
+__global__ __launch_bounds__(ST) void k_steer(SteerArgs A) {
+    const uint32_t i = blockIdx.x * ST + threadIdx.x;
+    const uint32_t m = min(i, A.n - 1u);
+    const uint32_t a = A.mv[m], b = A.tg[m];
+    const float s = A.step[m];
+    const uint32_t fl = A.flags ? A.flags[m] : STEER_ALL;
+    uint32_t err = 0;  // (device form only: the host form is checked on the host)
+    if (a >= A.max_slots || (b >= A.max_slots && b != GWAOI_NO_SLOT)) err |= STEER_E_SLOT;
+    if (fl & ~STEER_ALL) err |= STEER_E_INVAL;
+    if (!(fabsf(s) <= 3.402823466e+38f)) err |= STEER_E_NONFINITE;
+    // every load through a clamped index, none under a per-lane branch: the two ranks and the mover's
+    // record in one round trip, the two frame entries and records in the next
+    const uint32_t ac = min(a, A.max_slots - 1u), bc = min(b, A.max_slots - 1u);
+    uint32_t ra = A.info.rank[ac], rb = A.info.rank[bc];
+    uint32_t sp = reinterpret_cast<const uint32_t *>(A.slots)[SLOT_W * (size_t)ac + SST_SPACE];
+    float y = reinterpret_cast<const float *>(A.slots)[SLOT_W * (size_t)ac + POS_Y];
+    float yaw = reinterpret_cast<const float *>(A.slots)[SLOT_W * (size_t)ac + POS_Y + 2];
+    asm volatile("" : "+v"(ra), "+v"(rb), "+v"(sp), "+v"(y), "+v"(yaw));  // (issued together, none sunk under a branch)
+    bool on = false;
+    float x = 0.f, z = 0.f;
+    if (A.F.n) {  // (uniform: an empty frame has no entry 0 to clamp to)
+        const uint32_t ia = ra < A.F.n ? ra : 0u, ib = rb < A.F.n ? rb : 0u;
+        SlotSp Sa = ld_ss(A.F.ss, ia), Sb = ld_ss(A.F.ss, ib);
+        Rec16 Ra = ld_rec(A.F.rec, ia), Rb = ld_rec(A.F.rec, ib);
+        // (else the gate's && chain loads the seqs, and D, only in the lanes that got that far)
+        asm volatile("" : "+v"(Sa.slot), "+v"(Sa.sp), "+v"(Sb.slot), "+v"(Sb.sp), "+v"(Ra.x), "+v"(Ra.z), "+v"(Ra.s),
+                     "+v"(Rb.x), "+v"(Rb.z), "+v"(Rb.s));
+        float D = A.F.grid[Sa.sp].D;  // (a frame entry's space: valid whether or not it is the mover's)
+        asm volatile("" : "+v"(D));
+        // mover.IsInterestedIn(target), as k_related answers it (GWAOI_NO_SLOT is not in the frame)
+        on = !err && fl != 0u && b < A.max_slots && ra < A.F.n && rb < A.F.n && Sa.slot == a && Sb.slot == b &&
+             Sa.sp == Sb.sp && a != b && rel(Ra.x, Ra.z, Ra.s, Rb.x, Rb.z, Rb.s, D);
+        x = Ra.x;
+        z = Ra.z;
+        if (fl & GWAOI_STEER_MOVE) {  // mypos + Normalized(target - mypos, Y = 0) * step
+            float dx = Rb.x - x, dy = 0.0f, dz = Rb.z - z;
+            steer_normalize(dx, dy, dz);
+            x = x + dx * s;
+            y = y + dy * s;
+            z = z + dz * s;
+        }
+        if (fl & GWAOI_STEER_FACE) yaw = steer_dir_to_yaw(Rb.x - x, Rb.z - z);  // (from the new position)
+    }
+    if (i >= A.n) return;
+    // a Position the flush would refuse never reaches the slot record
+    if (on && !(fabsf(x) <= 3.402823466e+38f && fabsf(z) <= 3.402823466e+38f && yaw == yaw)) {
+        on = false;
+        err |= STEER_E_NONFINITE;
+    }
+    A.o_slot[i] = on && (fl & GWAOI_STEER_MOVE) ? a : SLOT_NONE;
+    A.o_x[i] = x;
+    A.o_z[i] = z;
+    A.o_sp[i] = sp;  // SST_SPACE (no op is queued: the frame's)
+    A.o_ms[i] = on ? a : SLOT_NONE;
+    A.out_applied[i] = on ? 1 : 0;
+    float *o = A.out_pos + 4 * (size_t)i;
+    o[0] = on ? x : 0.f;
+    o[1] = on ? y : 0.f;
+    o[2] = on ? z : 0.f;
+    o[3] = on ? yaw : 0.f;
+    if (on) {
+        // a plain store, as the decode's: this call's claims are larger than every claim applied so
+        // far.  Both words whatever the flags: the Position word doubles as the repeated-mover check.
+        const unsigned long long c = A.claim0 + i;
+        reinterpret_cast<ulonglong2 *>(A.cl)[a] = make_ulonglong2(c, c);
+    }
+    if (err) atomicOr(A.status, err);  // (rare: a dropped message)
+}
+
+// The survivors of the claim compare write their slot records: Position for MOVE, yaw for FACE, and
+// both sync flags.  A message whose store was overwritten by another message of the same mover is
+// dropped and reported.
+__global__ __launch_bounds__(ST) void k_steer_apply(SteerArgs A) {
+    const uint32_t i = blockIdx.x * ST + threadIdx.x;
+    if (i >= A.n) return;
+    const uint32_t s = A.o_ms[i];
+    if (s == SLOT_NONE) return;
+    float *o = A.out_pos + 4 * (size_t)i;
+    if (A.cl[2 * (size_t)s] != A.claim0 + i) {
+        A.o_slot[i] = SLOT_NONE;
+        A.out_applied[i] = 0;
+        o[0] = o[1] = o[2] = o[3] = 0.f;
+        atomicOr(A.status, STEER_E_INVAL);
+        return;
+    }
+    const uint32_t fl = A.flags ? A.flags[i] : STEER_ALL;
+    float *p = reinterpret_cast<float *>(A.pos + SLOT_U4 * (size_t)s);
+    if (fl & GWAOI_STEER_MOVE) {
+        p[0] = o[0];
+        p[1] = o[1];
+        p[2] = o[2];
+    }
+    if (fl & GWAOI_STEER_FACE) p[3] = o[3];
+    uint32_t *f = A.sst + SLOT_W * (size_t)s + SST_FLAGS;
+    *f = *f | SIDE_SIF;
+}
+
 // -------------------------------------------------------------- route ------
 struct RouteArgs {
     const uint32_t *ev;  // (a,b) pairs: [enters | leaves]
@@ -1522,6 +1672,7 @@ struct SyncState {
     std::vector<uint64_t> h_off_swc, h_off_swd;
     std::vector<uint32_t> sw_stamp, sw_gate;  // sw_gate: the batch's new gate indices
     uint32_t sw_epoch = 0;
+    PinnedBuf<uint32_t> h_steer;  // gwaoi_steer_batch: the status word on the host
 };
 
 namespace {
@@ -2201,19 +2352,13 @@ int collect_switch(gwaoi_world *w, const uint32_t *slots, const uint16_t *gate_i
     return GWAOI_OK;
 }
 
-int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
-    if (!w || (n && !payload)) return GWAOI_EINVAL;
-    if (on_device && (reinterpret_cast<uintptr_t>(payload) & 15u)) return GWAOI_EINVAL;
-    SyncState *S;
-    if (int rc = state(w, &S)) return rc;
-    if (world_view(w).in_flight) return GWAOI_ESTATE;  // a flush in flight reads the sync state's stream
-    if (!n) return GWAOI_OK;
-    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
-    // arena of the current flush (older chunks were consumed by earlier flushes)
+// `need` bytes (256-B aligned) of the current flush's arena: device memory that stays alive until
+// the flush that consumes the batch built in it (older chunks were consumed by earlier flushes).
+int arena_take(SyncState *S, size_t need, char **base) {
     uint64_t ticks_now;
     {
         gwaoi_info inf;
-        gwaoi_world_info(w, &inf);
+        gwaoi_world_info(S->w, &inf);
         ticks_now = inf.ticks;
     }
     if (S->arena_tick != ticks_now) {
@@ -2226,8 +2371,6 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
         for (auto &c : S->arena) c.used = 0;
         S->arena_tick = ticks_now;
     }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t need = 6 * al(n * 4) + al(4) + (on_device ? 0 : al(n * 32));
     SyncState::Chunk *ch = nullptr;
     for (auto &c : S->arena)
         if (c.buf.cap() - c.used >= need) {
@@ -2240,8 +2383,23 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
         S->arena.push_back(std::move(c));
         ch = &S->arena.back();
     }
-    char *base = ch->buf + ch->used;
+    *base = ch->buf + ch->used;
     ch->used += need;
+    return GWAOI_OK;
+}
+
+int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
+    if (!w || (n && !payload)) return GWAOI_EINVAL;
+    if (on_device && (reinterpret_cast<uintptr_t>(payload) & 15u)) return GWAOI_EINVAL;
+    SyncState *S;
+    if (int rc = state(w, &S)) return rc;
+    if (world_view(w).in_flight) return GWAOI_ESTATE;  // a flush in flight reads the sync state's stream
+    if (!n) return GWAOI_OK;
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t need = 6 * al(n * 4) + al(4) + (on_device ? 0 : al(n * 32));
+    char *base;
+    if (int rc = arena_take(S, need, &base)) return rc;
     uint32_t *o_slot = reinterpret_cast<uint32_t *>(base);
     float *o_x = reinterpret_cast<float *>(base + al(n * 4));
     float *o_z = reinterpret_cast<float *>(base + 2 * al(n * 4));
@@ -2284,6 +2442,112 @@ int decode(gwaoi_world *w, const uint8_t *payload, size_t n, bool on_device) {
     HIP_TRY(S->w, hipGetLastError());
     HIP_TRY(S->w, hipEventRecord(S->ndec_ev, S->st));
     return world_queue_decoded(w, o_slot, o_x, o_z, o_sp, n);
+}
+
+// gwaoi_steer_batch(_device): the decode's shape.  The batch arrays, the host form's uploaded
+// messages and its answers on the device all come from the flush's arena.
+int steer(gwaoi_world *w, const uint32_t *movers, const uint32_t *targets, const float *steps, const uint32_t *flags,
+          size_t n, uint8_t *out_applied, float *out_pos, bool on_device) {
+    if (!w || (n && (!movers || !targets || !steps || !out_applied || !out_pos))) return GWAOI_EINVAL;
+    SyncState *S;
+    if (int rc = state(w, &S)) return rc;
+    const WorldView v = world_view(w);
+    if (v.pending_ops) return GWAOI_ESTATE;  // (a flush in flight counts: the relation and the frame of one flush)
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    if (!on_device) {  // nothing happens on error: checked before any device work
+        int bad = GWAOI_OK;
+        for (size_t m = 0; m < n && bad != GWAOI_EBADSLOT; ++m) {
+            if (movers[m] >= v.max_slots || (targets[m] >= v.max_slots && targets[m] != GWAOI_NO_SLOT))
+                bad = GWAOI_EBADSLOT;
+            else if (flags && (flags[m] & ~STEER_ALL))
+                bad = GWAOI_EINVAL;
+            else if (!std::isfinite(steps[m]) && bad == GWAOI_OK)
+                bad = GWAOI_ENONFINITE;
+        }
+        if (bad == GWAOI_EBADSLOT || bad == GWAOI_EINVAL) return bad;
+        if (S->sw_stamp.empty()) S->sw_stamp.assign(S->max_slots, 0u);
+        if (++S->sw_epoch == 0) {  // (the stamps of 2^32 calls ago)
+            std::fill(S->sw_stamp.begin(), S->sw_stamp.end(), 0u);
+            S->sw_epoch = 1;
+        }
+        for (size_t m = 0; m < n; ++m) {
+            if (S->sw_stamp[movers[m]] == S->sw_epoch) return GWAOI_EINVAL;  // a mover named twice
+            S->sw_stamp[movers[m]] = S->sw_epoch;
+        }
+        if (bad != GWAOI_OK) return bad;  // GWAOI_ENONFINITE, the last in precedence
+    }
+    if (!n) return GWAOI_OK;
+    if (!S->h_steer)
+        if (int rc = alloc_pinned(S->w, S->h_steer, 1)) return rc;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t a4 = al(n * 4);
+    const size_t need = 5 * a4 + al(4) + (on_device ? 0 : 4 * a4 + al(n) + al(n * 16));
+    char *base;
+    if (int rc = arena_take(S, need, &base)) return rc;
+    if (int rc = push(S)) return rc;  // every earlier position and yaw write is visible
+    SteerArgs A{};
+    A.F = v.F;
+    A.info = v.info;
+    A.slots = S->slots;
+    A.n = (uint32_t)n;
+    A.max_slots = v.max_slots;
+    A.o_slot = reinterpret_cast<uint32_t *>(base);
+    A.o_x = reinterpret_cast<float *>(base + a4);
+    A.o_z = reinterpret_cast<float *>(base + 2 * a4);
+    A.o_sp = reinterpret_cast<uint32_t *>(base + 3 * a4);
+    A.o_ms = reinterpret_cast<uint32_t *>(base + 4 * a4);
+    A.status = reinterpret_cast<uint32_t *>(base + 5 * a4);
+    if (on_device) {
+        A.mv = movers;
+        A.tg = targets;
+        A.step = steps;
+        A.flags = flags;
+        A.out_applied = out_applied;
+        A.out_pos = out_pos;
+    } else {
+        char *in = base + 5 * a4 + al(4);
+        HIP_TRY(S->w, hipMemcpyAsync(in, movers, n * 4, hipMemcpyHostToDevice, S->st));
+        HIP_TRY(S->w, hipMemcpyAsync(in + a4, targets, n * 4, hipMemcpyHostToDevice, S->st));
+        HIP_TRY(S->w, hipMemcpyAsync(in + 2 * a4, steps, n * 4, hipMemcpyHostToDevice, S->st));
+        if (flags) HIP_TRY(S->w, hipMemcpyAsync(in + 3 * a4, flags, n * 4, hipMemcpyHostToDevice, S->st));
+        A.mv = reinterpret_cast<const uint32_t *>(in);
+        A.tg = reinterpret_cast<const uint32_t *>(in + a4);
+        A.step = reinterpret_cast<const float *>(in + 2 * a4);
+        A.flags = flags ? reinterpret_cast<const uint32_t *>(in + 3 * a4) : nullptr;
+        A.out_applied = reinterpret_cast<uint8_t *>(in + 4 * a4);
+        A.out_pos = reinterpret_cast<float *>(in + 4 * a4 + al(n));
+    }
+    A.claim0 = S->claim_next;
+    A.cl = S->cl;
+    A.sst = S->sst;
+    A.pos = S->pos;
+    S->claim_next += n;
+    HIP_TRY(S->w, hipMemsetAsync(A.status, 0, 4, S->st));
+    k_steer<<<cdivu(n, ST), ST, 0, S->st>>>(A);
+    k_steer_apply<<<cdivu(n, ST), ST, 0, S->st>>>(A);
+    HIP_TRY(S->w, hipGetLastError());
+    if (!on_device) {
+        HIP_TRY(S->w, hipMemcpyAsync(out_applied, A.out_applied, n, hipMemcpyDeviceToHost, S->st));
+        HIP_TRY(S->w, hipMemcpyAsync(out_pos, A.out_pos, n * 16, hipMemcpyDeviceToHost, S->st));
+    }
+    // the one host wait: the status word (and, in the host form, the answers)
+    HIP_TRY(S->w, hipMemcpyAsync(S->h_steer, A.status, 4, hipMemcpyDeviceToHost, S->st));
+    HIP_TRY(S->w, hipStreamSynchronize(S->st));
+    const uint32_t status = *S->h_steer;
+    if (int rc = world_queue_decoded(w, A.o_slot, A.o_x, A.o_z, A.o_sp, n)) return rc;
+    if (status & STEER_E_SLOT) {
+        world_set_error(w, "steer: messages with a slot >= max_slots are dropped");
+        return GWAOI_EBADSLOT;
+    }
+    if (status & STEER_E_INVAL) {
+        world_set_error(w, "steer: a flag bit outside MOVE | FACE, or a mover named twice (one of its messages applied)");
+        return GWAOI_EINVAL;
+    }
+    if (status & STEER_E_NONFINITE) {
+        world_set_error(w, "steer: messages with a non-finite step or a non-finite new position are dropped");
+        return GWAOI_ENONFINITE;
+    }
+    return GWAOI_OK;
 }
 
 }  // namespace
@@ -2777,6 +3041,18 @@ int gwaoi_nearest_batch_device(gwaoi_world *w, const uint32_t *d_slots, const ui
                                const uint32_t *d_wants, size_t n, uint32_t *d_out_slot, float *d_out_dist) {
     return gw::api_guard([&]() -> int {
     return gw::query_nearest(w, d_slots, d_masks, d_wants, n, d_out_slot, d_out_dist, true);
+    });
+}
+
+int gwaoi_steer_batch(gwaoi_world *w, const uint32_t *movers, const uint32_t *targets, const float *steps,
+                      const uint32_t *flags, size_t n, uint8_t *out_applied, float *out_pos) {
+    return gw::api_guard([&]() -> int { return gw::steer(w, movers, targets, steps, flags, n, out_applied, out_pos, false); });
+}
+
+int gwaoi_steer_batch_device(gwaoi_world *w, const uint32_t *d_movers, const uint32_t *d_targets, const float *d_steps,
+                             const uint32_t *d_flags, size_t n, uint8_t *d_out_applied, float *d_out_pos) {
+    return gw::api_guard([&]() -> int {
+    return gw::steer(w, d_movers, d_targets, d_steps, d_flags, n, d_out_applied, d_out_pos, true);
     });
 }
 

@@ -34,6 +34,10 @@
  *     (Monster.Tick, Monster.go:81,91)
  *   Monster.AI's nearest living Player: Entity.DistanceTo       gwaoi_entity_set_tag(_batch) +
  *     Entity.go:253-256, Vector3.go:22-28                         gwaoi_nearest_batch(_device)
+ *   Monster.Tick's chase: SetPosition(mypos +                  gwaoi_steer_batch(_device)
+ *     Normalized(target - mypos) * step)  examples/unity_demo/Monster.go:80-102
+ *   Entity.FaceTo / FaceToPos           Entity.go:1292-1304       (GWAOI_STEER_MOVE, GWAOI_STEER_FACE)
+ *     Vector3.DirToYaw / Normalize      Vector3.go:44-77
  *
  * Entity ids and client ids are the reference's 16-byte strings
  * (common.ENTITYID_LENGTH = common.CLIENTID_LENGTH = uuid.UUID_LENGTH = 16,
@@ -326,6 +330,79 @@ int gwaoi_nearest_batch(gwaoi_world *w, const uint32_t *slots, const uint32_t *m
 /* Same; every array in device memory, the outputs complete on return. */
 int gwaoi_nearest_batch_device(gwaoi_world *w, const uint32_t *d_slots, const uint32_t *d_masks,
                                const uint32_t *d_wants, size_t n, uint32_t *d_out_slot, float *d_out_dist);
+
+/* ---- server-driven movement ------------------------------------------------- */
+/* Monster.Tick's step for a batch of n entities (Monster.go:80-102): move toward a target and face
+ * it, on the GPU, from the positions the device already holds.  With gwaoi_nearest_batch_device
+ * giving the targets (the IsInterestedIn gate is part of this call) the whole NPC step needs no
+ * position on the host: nearest -> steer -> flush -> collect.
+ *
+ * Messages.  Message m is (movers[m], targets[m], steps[m], flags[m]); flags == NULL means
+ * MOVE | FACE for every message.
+ * Gate.  A message applies iff flags[m] != 0 and movers[m].IsInterestedIn(targets[m]) on the
+ * relation of the last committed flush: exactly gwaoi_related_batch's answer for the pair (both
+ * branches of Monster.Tick test it, Monster.go:81,91).  A message that does not apply gets
+ * out_applied[m] = 0 and four zero words in out_pos, changes nothing and is not an error: a mover or
+ * target outside the frame, in another space or never bound, mover == target, and targets[m] ==
+ * GWAOI_NO_SLOT, so that gwaoi_nearest_batch_device's output can be passed on as it is.
+ * Snapshot.  Every message reads the state before the call: x and z of both entities from the frame
+ * (the AOI position of the last flush, gwaoi_nearest_batch's convention), the mover's y and yaw from
+ * its slot record.  A target that is itself a mover of the batch is seen at its old position.
+ * Arithmetic.  The reference's on amd64, float32 step by step, nothing fused, IEEE division,
+ * denormals kept.  a is the mover, b the target, s = steps[m].
+ *   MOVE: dx = b.x - a.x, dy = 0, dz = b.z - a.z; Vector3.Normalize as written (Vector3.go:64-72):
+ *   d = (float)sqrt((double)(dx*dx + dy + dy + dz*dz)), the sum taken left to right; d == 0 leaves
+ *   the direction as it is (also when dx*dx underflowed to zero with dx != 0), otherwise each
+ *   component is divided by d.  Position' = (a.x + nx*s, a.y + ny*s, a.z + nz*s).  The effect is
+ *   setPositionYaw(Position', yaw unchanged, fromClient = false): a Moved(x', z'), Position and both
+ *   sync flags.
+ *   FACE: after the move, from the new position: dx = b.x - x', dz = b.z - z', the same Normalize,
+ *   then Vector3.DirToYaw (Vector3.go:45-62) in float64: acos(X), 2 pi - yaw if Z < 0, / pi * 180,
+ *   yaw <= 90 ? 90 - yaw : 90 + (360 - yaw), cast to float32.  The effect is SetYaw: yaw and both
+ *   sync flags.
+ *   |X| <= 1 whenever fl(dx*dx) is a normal float32, zero or +inf: d >= fl(sqrt(fl(dx*dx))) = |dx|
+ *   by monotonicity (a sum that overflows gives d = +inf and the direction (0, 0, 0)), so no NaN
+ *   arises from such coordinates.  The one exception is the reference's own: for 1.1e-19 > |dx| >
+ *   2.6e-23 the square is a denormal with fewer than 24 bits, it may round down, and then d < |dx|
+ *   and X slightly above 1 (1.0097 for dx = 1e-22, dz = 0): acos(X) is NaN there in the reference
+ *   too, and X * step can overflow for a step near the largest float32.
+ * Yaw is not bit-exact.  Positions are the reference's bit for bit; yaw goes through a float64 acos
+ * that is not the Go runtime's: it equals the reference's to within one float32 ulp (as an angle,
+ * modulo 360: DirToYaw jumps from 0 to 360 at yaw = 90).
+ * out_applied[m] is 1 iff message m applied; out_pos[4m .. 4m+4) is the mover's x, y, z, yaw after it.
+ * Order.  The applied MOVE messages are one device Moved batch in message order, queued after
+ * everything before it as a decoded packet is; Position and yaw take last-writer claims like every
+ * other write, so a later gwaoi_set_position_yaw or packet for the same slot in the same flush wins,
+ * as the sequential calls would leave it.
+ * State.  GWAOI_ESTATE with ops queued or a flush in flight, as for the reads: the call needs the
+ * relation and the frame of one flush.  A call with n > 0 counts as a queued op: flush before the
+ * next read, collect or steer (one steer call per loop iteration, holding every entity whose Tick
+ * fires in it).
+ * Movers are distinct (each message would have to read what the previous one wrote); targets may
+ * repeat freely.  Host form: a repeated mover is GWAOI_EINVAL and nothing happens.  Device form: one
+ * message of a repeated mover applies (which one is unspecified), the others are dropped with
+ * out_applied = 0, and the call returns GWAOI_EINVAL.
+ * Errors, host form (before any device work, nothing changed): null w, or a null array other than
+ * flags with n > 0: GWAOI_EINVAL; a flag bit outside MOVE | FACE: GWAOI_EINVAL; a mover >= max_slots
+ * or a target >= max_slots other than GWAOI_NO_SLOT: GWAOI_EBADSLOT; a non-finite step:
+ * GWAOI_ENONFINITE.
+ * Errors, device form (every array in device memory of the world's GPU, the outputs complete on
+ * return): an offending message is dropped (out_applied = 0), the others are delivered and the call
+ * returns the code; of several, GWAOI_EBADSLOT, then GWAOI_EINVAL, then GWAOI_ENONFINITE.
+ * Both forms: a message whose new x or z is not finite, or whose yaw is NaN (the exception above;
+ * where the reference would go on with a NaN yaw or an infinite Position), is dropped the same way
+ * and the call returns GWAOI_ENONFINITE, the host form with the other answers delivered; the slot
+ * record never holds a position the flush would refuse.  The world stays usable after every error. */
+#define GWAOI_STEER_MOVE 1u   /* Monster.go:92-97: SetPosition(mypos + Normalized(dir) * step)      */
+#define GWAOI_STEER_FACE 2u   /* Entity.FaceTo(target), Entity.go:1292-1304 (after the move, if both) */
+
+int gwaoi_steer_batch(gwaoi_world *w, const uint32_t *movers, const uint32_t *targets, const float *steps,
+                      const uint32_t *flags /* NULL: MOVE | FACE */, size_t n,
+                      uint8_t *out_applied /* n */, float *out_pos /* 4n: x, y, z, yaw */);
+/* Same; every array in device memory of the world's GPU. */
+int gwaoi_steer_batch_device(gwaoi_world *w, const uint32_t *d_movers, const uint32_t *d_targets,
+                             const float *d_steps, const uint32_t *d_flags /* NULL: MOVE | FACE */, size_t n,
+                             uint8_t *d_out_applied, float *d_out_pos);
 
 #ifdef __cplusplus
 }
