@@ -154,14 +154,94 @@ class StagePool {
     bool stop_ = false;
 };
 
-// A call made while a flush is in flight (gwaoi_tick_begin .. _end): validated
-// and given its seq at call time, queued for the next flush at the commit.
-struct Deferred {
-    enum Kind : uint8_t { MOVED, ENTER, LEAVE, RUN } kind;
+// The move staging and the only code that writes it.  Host move batches are staged as
+// [slots | x | z | space] (n words each) at the fill of the current half, sent on the copy stream
+// and queued as device runs over those words.  Two halves: calls made while a flush is in flight
+// stage into the half that flush does not read; a launch flips them.  Words asked for and consumed:
+//   gwaoi_moved_batch         asks 4n, consumes what it sent: 4n with the space column, else 3n
+//   gwaoi_moved_batch_stage   asks 4n and reserves them; _commit consumes 4n whatever k and the column
+//   gwaoi_moved_batch_pinned  asks 3n and consumes 3n (it never carries a space column)
+struct MoveStaging {
+    gw::PinnedBuf<uint32_t> h[2];
+    gw::DevBuf<uint32_t> d[2];  // (a half's capacity in words is d[half].cap())
+    size_t used[2] = {0, 0};    // words of a half that queued batches point into: its fill
+    int cur = 0;                // the half that calls stage into
+    size_t resv_n = 0, resv_at = 0;  // the one reservation: moves (0: none) at this word ...
+    int resv_half = 0;               // ... of this half; void while a launch has made the other current
+    gw::Stream copy_st;         // staging H2D copies
+    gw::Event copy_ev;          // recorded after the last staging copy
+    bool copy_pending = false;  // the flush must wait for copy_ev
+
+    int create() { return copy_st.create(hipStreamNonBlocking) || copy_ev.create(hipEventDisableTiming); }
+    void drain() {
+        if (copy_st) (void)hipStreamSynchronize(copy_st);
+    }
+    // Room for `words` more at the fill: GWAOI_OK, a failed allocation's status, or GWAOI_ECAPACITY (with a
+    // message if `what` is given): none without moving a buffer a queued batch or a reservation points into.
+    int room(std::string &err, size_t words, bool in_flight, const char *what) {
+        if (resv_n || (used[cur] && used[cur] + words > d[cur].cap())) {
+            if (what) err = std::string("staging memory holds this flush's batches: flush before ") + what;
+            return GWAOI_ECAPACITY;
+        }
+        if (used[cur] + words <= d[cur].cap()) return GWAOI_OK;
+        const size_t c = std::max<size_t>({2 * words, 2 * d[cur].cap(), (size_t)4 << 16});
+        HIP_TRY(err, hipStreamSynchronize(copy_st));  // no staging copy may still read the old buffer
+        if (int rc = grow_half(err, cur, c)) return rc;
+        // grow the other half alike while no flush reads it, so that the first flush that stages
+        // into it (the next one begun with gwaoi_tick_begin) does not pay the pinned allocation
+        if (!in_flight && used[cur ^ 1] == 0 && d[cur ^ 1].cap() < c) (void)grow_half(err, cur ^ 1, c);
+        return GWAOI_OK;
+    }
+    // a half's pinned and device buffers grow together, or the half is left empty
+    int grow_half(std::string &err, int q, size_t c) {
+        d[q].reset();
+        int rc = gw::alloc_pinned(err, h[q], c);
+        if (!rc && (rc = gw::alloc_all(err, d[q], c))) h[q].reset();
+        return rc;
+    }
+    size_t fill() const { return used[cur]; }
+    uint32_t *host(size_t at) const { return h[cur] + at; }  // word `at` of the current half
+    uint32_t *dev(size_t at) const { return d[cur] + at; }
+    // nsrc sources of `words` words each to consecutive device words from `at`; consumes `take`
+    int send(std::string &err, size_t at, const void *const *src, int nsrc, size_t words, size_t take) {
+        for (int a = 0; a < nsrc; ++a)
+            HIP_TRY(err, hipMemcpyAsync(dev(at) + a * words, src[a], words * sizeof(uint32_t), hipMemcpyHostToDevice, copy_st));
+        HIP_TRY(err, hipEventRecord(copy_ev, copy_st));
+        copy_pending = true;
+        used[cur] += take;
+        return GWAOI_OK;
+    }
+    int wait(std::string &err, hipStream_t st) {  // the copies land before `st` goes on
+        if (copy_pending) HIP_TRY(err, hipStreamWaitEvent(st, copy_ev, 0));
+        copy_pending = false;
+        return GWAOI_OK;
+    }
+    void flip() {  // a launch: calls made in flight stage into the other half (free: its flush has ended)
+        cur ^= 1;
+        used[cur] = 0;
+    }
+    void release() { used[cur] = 0; }  // the current half's batches were read (a sparse flush)
+    uint32_t *reserve(size_t n) {      // n moves at the fill: their pinned words
+        resv_n = n;
+        resv_at = used[cur];
+        resv_half = cur;
+        return host(resv_at);
+    }
+    size_t unreserve() { return std::exchange(resv_n, 0); }  // its moves (0: there was none)
+};
+
+// A validated host call with its seq.
+struct HostOp {
+    enum Kind : uint8_t { MOVED, ENTER, LEAVE } kind;
     uint32_t slot, space;
     float x, z;
     uint64_t seq;
-    Run run;  // RUN: a staged or device batch
+};
+// A call made while a flush is in flight: a host op or (is_run) a batch, queued for the next flush at the commit.
+struct Deferred {
+    bool is_run;
+    HostOp op;
+    Run run;
 };
 struct DeferredBox {  // Enter/Moved positions of a deferred staged batch, per space
     uint32_t space;
@@ -303,13 +383,7 @@ struct gwaoi_world {
     uint32_t dev_app = 0;     // entries the queued device Enter batches append to S'
     bool dev_struct = false;  // a device Enter/Leave batch is queued
     bool slots_stale = false; // the host mirror misses device Enter/Leave batches of committed flushes
-    // host move batches (gwaoi_moved_batch) staged as [slots | x | z | space] in pinned memory and sent
-    // with one async H2D each (copy stream); they then run as device batches.  Two halves: the calls
-    // queued while a flush is in flight stage into the half that flush does not read.
-    gw::PinnedBuf<uint32_t> h_stage[2];
-    gw::DevBuf<uint32_t> d_stage[2];
-    size_t stage_cap[2] = {0, 0}, stage_used[2] = {0, 0};
-    int stage_cur = 0;
+    MoveStaging staging;  // host move batches on their way to the device
     // sparse flush (gwaoi_sparse.hip): per-op counts and offsets, and the host ops' upload buffer
     // (sp_ops_layout: pinned -> device in one copy); off with GWAOI_F_NO_SPARSE
     gw::DevBuf<uint32_t> sp_cnt;
@@ -321,10 +395,6 @@ struct gwaoi_world {
     uint32_t sp_scr_cap = 512;
     bool sparse_fused = true;
     bool sparse_on = true;
-    // zero-copy batch (gwaoi_moved_batch_stage / _commit): the caller fills [slots | x | z | space]
-    size_t resv_n = 0;        // moves reserved (0: no reservation)
-    uint32_t *resv_h = nullptr, *resv_d = nullptr;  // views into h_stage / d_stage[resv_half]
-    int resv_half = 0;
     // event copies to the host beside the next flush (gwaoi_tick_finish, GWAOI_END_HOST / _PAIRS)
     gw::Stream out_st;
     gw::Event out_ev;
@@ -335,9 +405,6 @@ struct gwaoi_world {
     uint64_t out_n_enter = 0, out_n_leave = 0;
     // GWAOI_F_UNIQUE_MOVES: the Moved batches of one flush never repeat a slot (no claims, no fixup)
     bool unique_moves = false;
-    gw::Stream copy_st;  // staging H2D copies
-    gw::Event copy_ev;   // recorded after the last staging copy
-    bool copy_pending = false;      // the flush must wait for copy_ev
     StagePool pool;
     unsigned stage_threads = 8;  // host threads validating + staging one big batch
     std::vector<uint32_t> new_slots;
@@ -579,31 +646,35 @@ void mark_appended(gwaoi_world *w, uint32_t slot) {
     }
 }
 
+// The one way a validated host call joins the next flush's op queue (a Leave: space SP_DEAD, no
+// position): when the call is made, or at the commit of the flush that was in flight then.
+void queue_host_op(gwaoi_world *w, const HostOp &q) {
+    if (q.kind != HostOp::LEAVE) note_pending_bbox(w->spaces[q.space], q.x, q.z);
+    if (q.kind == HostOp::ENTER) mark_appended(w, q.slot);
+    if (q.kind != HostOp::MOVED) {
+        w->touched.push_back(q.slot);
+        w->space_ops_queued = true;  // (again at the replay: the launch in between cleared it)
+    }
+    push_host_op(w, q.slot, q.x, q.z, q.space, q.seq);
+}
+
+// A validated host call: queued now, or deferred while a flush is in flight.
+void submit(gwaoi_world *w, const HostOp &q) {
+    // at call time, also in flight: a batch staged after an Enter or Leave carries the space column
+    if (q.kind != HostOp::MOVED) w->space_ops_queued = true;
+    if (w->in_flight) w->deferred.push_back(Deferred{false, q, Run{}});
+    else queue_host_op(w, q);
+}
+
 // Queue the calls deferred while a flush was in flight, in call order, as if
 // they had been made now (their seqs were taken at call time).
 void replay_deferred(gwaoi_world *w) {
     for (const Deferred &q : w->deferred) {
-        switch (q.kind) {
-            case Deferred::ENTER:
-                note_pending_bbox(w->spaces[q.space], q.x, q.z);
-                mark_appended(w, q.slot);
-                w->touched.push_back(q.slot);
-                push_host_op(w, q.slot, q.x, q.z, q.space, q.seq);
-                w->space_ops_queued = true;
-                break;
-            case Deferred::LEAVE:
-                w->touched.push_back(q.slot);
-                push_host_op(w, q.slot, 0.f, 0.f, gw::SP_DEAD, q.seq);
-                w->space_ops_queued = true;
-                break;
-            case Deferred::MOVED:
-                note_pending_bbox(w->spaces[q.space], q.x, q.z);
-                push_host_op(w, q.slot, q.x, q.z, q.space, q.seq);
-                break;
-            case Deferred::RUN:
-                w->runs.push_back(q.run);
-                w->n_ops += q.run.dn;
-                break;
+        if (!q.is_run) {
+            queue_host_op(w, q.op);
+        } else {
+            w->runs.push_back(q.run);
+            w->n_ops += q.run.dn;
         }
     }
     for (const DeferredBox &b : w->deferred_boxes) {
@@ -612,17 +683,6 @@ void replay_deferred(gwaoi_world *w) {
     }
     w->deferred.clear();
     w->deferred_boxes.clear();
-}
-
-void defer(gwaoi_world *w, Deferred::Kind k, uint32_t slot, uint32_t space, float x, float z, uint64_t seq) {
-    Deferred q{};
-    q.kind = k;
-    q.slot = slot;
-    q.space = space;
-    q.x = x;
-    q.z = z;
-    q.seq = seq;
-    w->deferred.push_back(q);
 }
 
 Run device_run(const uint32_t *ds, const float *dx, const float *dz, size_t n) {
@@ -645,7 +705,7 @@ void queue_run(gwaoi_world *w, Run r) {
     }
     if (w->in_flight) {
         Deferred q{};
-        q.kind = Deferred::RUN;
+        q.is_run = true;
         q.run = r;
         w->deferred.push_back(q);
         return;
@@ -921,11 +981,7 @@ int flush_open(gwaoi_world *w, DevFrame &Fn, const gw::FlushPlan &plan, hipStrea
         Fn.hgrid.assign(w->h_grid.get(), w->h_grid + ns);
     }
     // the staged move batches' H2D copies (copy stream) land before the flush reads them
-    if (w->copy_pending) {
-        HIP_TRY(w->last_error, hipStreamWaitEvent(*st, w->copy_ev, 0));
-        w->copy_pending = false;
-    }
-    return GWAOI_OK;
+    return w->staging.wait(w->last_error, *st);
 }
 
 // Op j0 .. of the flush as the single-pass apply takes a device run.
@@ -1131,8 +1187,7 @@ int record_flight(gwaoi_world *w, FlushSet &S, const gw::FlushPlan &plan, EvCaps
     w->launch_set ^= 1;
     w->fl.touched_alive.resize(w->touched.size());
     for (size_t i = 0; i < w->touched.size(); ++i) w->fl.touched_alive[i] = w->alive[w->touched[i]];
-    w->stage_cur ^= 1;  // calls made in flight stage into the other half (free: its flush has ended)
-    w->stage_used[w->stage_cur] = 0;
+    w->staging.flip();
     w->space_ops_queued = false;
     w->gen_launch = w->gen;
     return GWAOI_OK;
@@ -1374,7 +1429,7 @@ constexpr size_t kSpOpsBytes = 20 * kSparseMaxOps;
 int sparse_try(gwaoi_world *w) {
     if (!w->sparse_on || w->in_flight || w->n_ops == 0 || w->n_ops > kSparseMaxOps || !w->new_slots.empty() ||
         w->space_ops_queued || w->dev_app || w->dev_struct || w->dev_seq_pending || !w->deferred.empty() ||
-        w->resv_n || w->ticks == 0 || w->runs.size() != 1)
+        w->staging.resv_n || w->ticks == 0 || w->runs.size() != 1)
         return 1;
     const Run &run = w->runs[0];
     // one stretch of host calls, or one host batch staged as a device batch (validated on the host,
@@ -1423,9 +1478,8 @@ int sparse_try(gwaoi_world *w) {
         d_x = reinterpret_cast<const float *>(w->d_sp_ops + kSpX);
         d_z = reinterpret_cast<const float *>(w->d_sp_ops + kSpZ);
         d_seq = reinterpret_cast<const unsigned long long *>(w->d_sp_ops + kSpSeq);
-    } else if (w->copy_pending) {  // the staged batch's H2D lands first
-        HIP_TRY(w->last_error, hipStreamWaitEvent(st, w->copy_ev, 0));
-        w->copy_pending = false;
+    } else if ((rc = w->staging.wait(w->last_error, st))) {  // the staged batch's H2D lands first
+        return rc;
     }
     const uint32_t tick_id = ++w->tick_id;
     gw::TickOut *res = reinterpret_cast<gw::TickOut *>(S.h_out.dev());
@@ -1472,7 +1526,7 @@ int sparse_try(gwaoi_world *w) {
     w->seq_floor = w->seq_next;
     w->ticks++;
     // the staged batch was read (the stream was waited for): its staging words are free again
-    if (run.device) w->stage_used[w->stage_cur] = 0;
+    if (run.device) w->staging.release();
     return GWAOI_OK;
 }
 
@@ -1485,7 +1539,7 @@ bool speculative_ok(gwaoi_world *w) {
         return false;
     size_t n = 0;
     for (const Deferred &q : w->deferred) {
-        if (q.kind != Deferred::RUN || !q.run.device || q.run.dseq || q.run.dsp) return false;
+        if (!q.is_run || !q.run.device || q.run.dseq || q.run.dsp) return false;
         n += q.run.dn;
     }
     return n <= w->max_slots;
@@ -1530,7 +1584,7 @@ int gwaoi_world_destroy(gwaoi_world *w) {
 #endif
     if (w->stream) (void)hipStreamSynchronize(w->stream);
     if (w->early_st) (void)hipStreamSynchronize(w->early_st);
-    if (w->copy_st) (void)hipStreamSynchronize(w->copy_st);
+    w->staging.drain();
     if (w->out_st) (void)hipStreamSynchronize(w->out_st);
     if (w->sync) gw::sync_destroy(w->sync);
     w->sync = nullptr;
@@ -1580,7 +1634,7 @@ int gwaoi_world_create(const gwaoi_config *cfg, gwaoi_world **out) {
         return GWAOI_EDEVICE;
     }
     if (w->early_st.create(hipStreamNonBlocking) || w->stream.create(hipStreamNonBlocking) ||
-        w->copy_st.create(hipStreamNonBlocking) || w->copy_ev.create(hipEventDisableTiming) ||
+        w->staging.create() ||
         w->out_st.create(hipStreamNonBlocking) || w->out_ev.create(hipEventDisableTiming))
         return fail(GWAOI_EDEVICE);
     const size_t N = w->max_slots;
@@ -1729,6 +1783,24 @@ uint64_t take_seq(gwaoi_world *w, const uint64_t *seq) {
     return s;
 }
 
+// A validated Enter / Leave: the liveness bookkeeping, then the op (a Leave's seq is never compared).
+void enter_valid(gwaoi_world *w, uint32_t space, uint32_t slot, float x, float z, const uint64_t *seq) {
+    w->alive[slot] = 1;
+    w->space_of[slot] = space;
+    w->n_alive++;
+    if (w->sync) gw::sync_note_slot(w->sync, slot, space);
+    w->spaces[space].alive++;
+    submit(w, HostOp{HostOp::ENTER, slot, space, x, z, take_seq(w, seq)});
+}
+void leave_valid(gwaoi_world *w, uint32_t slot) {
+    w->alive[slot] = 0;
+    w->spaces[w->space_of[slot]].alive--;
+    w->space_of[slot] = gw::SP_DEAD;
+    w->n_alive--;
+    if (w->sync) gw::sync_note_slot(w->sync, slot, gw::SP_DEAD);
+    submit(w, HostOp{HostOp::LEAVE, slot, gw::SP_DEAD, 0.f, 0.f, w->seq_next});
+}
+
 int enter_impl(gwaoi_world *w, uint32_t space, uint32_t slot, float x, float z, const uint64_t *seq) {
     if (!w) return GWAOI_EINVAL;
     GW_LIVE(w);
@@ -1739,69 +1811,26 @@ int enter_impl(gwaoi_world *w, uint32_t space, uint32_t slot, float x, float z, 
     if (w->sync && gw::sync_slot_plain(w->sync, slot)) return GWAOI_ESTATE;  // in a space without AOI
     if (!finite2(x, z)) return GWAOI_ENONFINITE;
     if (int rc = check_seq(w, seq)) return rc;
-    w->alive[slot] = 1;
-    w->space_of[slot] = space;
-    w->n_alive++;
-    if (w->sync) gw::sync_note_slot(w->sync, slot, space);
-    SpaceHost &S = w->spaces[space];
-    S.alive++;
-    const uint64_t sq = take_seq(w, seq);
-    w->space_ops_queued = true;
-    if (w->in_flight) {
-        defer(w, Deferred::ENTER, slot, space, x, z, sq);
-        return GWAOI_OK;
-    }
-    note_pending_bbox(S, x, z);
-    mark_appended(w, slot);
-    w->touched.push_back(slot);
-    push_host_op(w, slot, x, z, space, sq);
+    enter_valid(w, space, slot, x, z, seq);
     return GWAOI_OK;
+}
+
+// The checks of gwaoi_moved on one move, in its order; *sp: the slot's space.  A live slot has a
+// space (space_of == SP_DEAD <=> !alive): one random lookup per move.
+inline int check_move(const uint32_t *space_of, uint32_t max_slots, uint32_t slot, float x, float z, uint32_t *sp) {
+    if (slot >= max_slots) return GWAOI_EBADSLOT;
+    if ((*sp = space_of[slot]) == gw::SP_DEAD) return GWAOI_ESTATE;
+    return finite2(x, z) ? GWAOI_OK : GWAOI_ENONFINITE;
 }
 
 int moved_impl(gwaoi_world *w, uint32_t slot, float x, float z, const uint64_t *seq) {
     if (!w) return GWAOI_EINVAL;
     GW_LIVE(w);
     if (int rc = host_slots(w)) return rc;
-    if (slot >= w->max_slots) return GWAOI_EBADSLOT;
-    if (!w->alive[slot]) return GWAOI_ESTATE;
-    if (!finite2(x, z)) return GWAOI_ENONFINITE;
+    uint32_t sp;
+    if (int rc = check_move(w->space_of.data(), w->max_slots, slot, x, z, &sp)) return rc;
     if (int rc = check_seq(w, seq)) return rc;
-    const uint64_t sq = take_seq(w, seq);
-    if (w->in_flight) {
-        defer(w, Deferred::MOVED, slot, w->space_of[slot], x, z, sq);
-        return GWAOI_OK;
-    }
-    note_pending_bbox(w->spaces[w->space_of[slot]], x, z);
-    push_host_op(w, slot, x, z, w->space_of[slot], sq);
-    return GWAOI_OK;
-}
-
-
-// Room for `words` more staged words.  1: no room without moving a buffer that a queued
-// batch still points into (the caller then queues the batch as host ops).
-int ensure_stage(gwaoi_world *w, size_t words) {
-    const int h = w->stage_cur;
-    // an open reservation (gwaoi_moved_batch_stage) owns the words past stage_used until its commit:
-    // nothing else may stage into them, and the buffer it points into must not move
-    if (w->resv_n) return 1;
-    if (w->stage_used[h] + words <= w->stage_cap[h]) return GWAOI_OK;
-    if (w->stage_used[h]) return 1;
-    const size_t cap = std::max<size_t>({2 * words, 2 * w->stage_cap[h], (size_t)4 << 16});
-    HIP_TRY(w->last_error, hipStreamSynchronize(w->copy_st));  // no staging copy may still read the old buffer
-    // a half's pinned and device buffers grow together, or the half is left empty
-    auto grow_half = [&](int q) {
-        w->stage_cap[q] = 0;
-        w->d_stage[q].reset();
-        int rc = gw::alloc_pinned(w->last_error, w->h_stage[q], cap);
-        if (!rc && (rc = gw::alloc_all(w->last_error, w->d_stage[q], cap))) w->h_stage[q].reset();
-        if (!rc) w->stage_cap[q] = cap;
-        return rc;
-    };
-    if (int rc = grow_half(h)) return rc;
-    // grow the other half alike while no flush reads it, so that the first flush that stages
-    // into it (the next one begun with gwaoi_tick_begin) does not pay the pinned allocation
-    const int o = h ^ 1;
-    if (!w->in_flight && w->stage_used[o] == 0 && w->stage_cap[o] < cap) (void)grow_half(o);
+    submit(w, HostOp{HostOp::MOVED, slot, sp, x, z, take_seq(w, seq)});
     return GWAOI_OK;
 }
 
@@ -1817,7 +1846,6 @@ size_t stage_chunk(const gwaoi_world *w, const uint32_t *slots, const float *x, 
                    size_t lo, size_t hi, uint32_t *h, bool with_space, StageBox *boxes, int *st) {
     uint32_t *hs = h, *hsp = h + 3 * n;
     float *hx = reinterpret_cast<float *>(h + n), *hz = reinterpret_cast<float *>(h + 2 * n);
-    // a live slot has a space (space_of == SP_DEAD <=> !alive): one random lookup per move
     const uint32_t *space_of = w->space_of.data();
     const uint32_t ms = w->max_slots;
     // The running box of the current space stays in registers: updated through a StageBox in
@@ -1838,10 +1866,8 @@ size_t stage_chunk(const gwaoi_world *w, const uint32_t *slots, const float *x, 
         if (i + 16 < hi) __builtin_prefetch(space_of + std::min(slots[i + 16], ms - 1));
         const uint32_t sl = slots[i];
         const float xi = x[i], zi = z[i];
-        if (sl >= ms) { *st = GWAOI_EBADSLOT; return i; }
-        const uint32_t sp = space_of[sl];
-        if (sp == gw::SP_DEAD) { *st = GWAOI_ESTATE; return i; }
-        if (!finite2(xi, zi)) { *st = GWAOI_ENONFINITE; return i; }
+        uint32_t sp;
+        if (const int bad = check_move(space_of, ms, sl, xi, zi, &sp)) { *st = bad; return i; }
         hs[i] = sl; hx[i] = xi; hz[i] = zi;
         if (with_space) hsp[i] = sp;
         if (sp != bsp) {
@@ -1859,7 +1885,38 @@ size_t stage_chunk(const gwaoi_world *w, const uint32_t *slots, const float *x, 
     return hi;
 }
 
-// A host move batch with room in the staging area (ensure_stage): validate + stage it on up to
+// A staged batch's per-space boxes join the pending boxes: now, or with the deferred calls at the commit.
+void note_staged_boxes(gwaoi_world *w, const StageBox *boxes, size_t nsp) {
+    for (size_t sp = 0; sp < nsp; ++sp) {
+        const StageBox &b = boxes[sp];
+        if (!b.any) continue;
+        if (w->in_flight) {
+            w->deferred_boxes.push_back(DeferredBox{(uint32_t)sp, b.x0, b.z0, b.x1, b.z1});
+        } else {
+            note_pending_bbox(w->spaces[sp], b.x0, b.z0);
+            note_pending_bbox(w->spaces[sp], b.x1, b.z1);
+        }
+    }
+}
+
+// Send the n moves staged at word `at` and queue a device run over the first k of them.  src: the
+// caller's three arrays (gwaoi_moved_batch_pinned: three copies), or nullptr for the half's own
+// pinned words (one copy, with the space column if present).  take: see MoveStaging.
+int send_staged(gwaoi_world *w, size_t at, size_t n, size_t k, bool with_space, bool checked, size_t take, const void *const *src) {
+    MoveStaging &S = w->staging;
+    const uint32_t *d = S.dev(at);
+    const void *const staged = S.host(at);
+    if (int rc = src ? S.send(w->last_error, at, src, 3, n, take)
+                     : S.send(w->last_error, at, &staged, 1, (with_space ? 4 : 3) * n, take))
+        return rc;
+    Run r = device_run(d, reinterpret_cast<const float *>(d + n), reinterpret_cast<const float *>(d + 2 * n), k);
+    r.dsp = with_space ? d + 3 * n : nullptr;
+    r.checked = checked;
+    queue_run(w, r);
+    return GWAOI_OK;
+}
+
+// A host move batch with room in the staging area (MoveStaging::room): validate + stage it on up to
 // kStageThreads host threads, send it with one async H2D and queue it as a device batch with seqs
 // seq_next.. and the slot's space at call time (explicit, so a slot that entered earlier in this
 // flush moves exactly as a host op would).  Nothing is queued if any move is rejected.
@@ -1867,45 +1924,55 @@ constexpr size_t kStageThreadMin = 1 << 13;  // moves per extra thread (65,536 m
 constexpr size_t kStageMin = 64;             // host move batches of this many moves or more are staged
 
 int stage_moves(gwaoi_world *w, const uint32_t *slots, const float *x, const float *z, size_t n) {
-    const int half = w->stage_cur;
     // the space column is needed only when an Enter/Leave of this flush precedes the batch (a slot
     // that entered in this flush must move in its new space); otherwise every slot keeps its space
     const bool with_space = w->space_ops_queued;
-    const size_t words = (with_space ? 4 : 3) * n;
-    uint32_t *h = w->h_stage[half] + w->stage_used[half], *d = w->d_stage[half] + w->stage_used[half];
+    const size_t at = w->staging.fill();
+    uint32_t *h = w->staging.host(at);
     const size_t nsp = std::max(1u, w->n_space_ids);
     unsigned T = (unsigned)std::min<size_t>(w->stage_threads, std::max<size_t>(1, n / kStageThreadMin));
     T = std::min(T, std::max(1u, std::thread::hardware_concurrency()));
     const size_t stride = nsp + 4;  // >= 64 B between the threads' boxes: no false sharing
     std::vector<StageBox> boxes((size_t)T * stride, StageBox{0, 0, 0, 0, false});
-    std::vector<size_t> bad(T, 0);
     std::vector<int> st(T, GWAOI_OK);
     const size_t chunk = (n + T - 1) / T;
     w->pool.run(T, [&](unsigned t) {
         const size_t lo = std::min(n, t * chunk), hi = std::min(n, lo + chunk);
-        bad[t] = stage_chunk(w, slots, x, z, n, lo, hi, h, with_space, boxes.data() + (size_t)t * stride, &st[t]);
+        stage_chunk(w, slots, x, z, n, lo, hi, h, with_space, boxes.data() + (size_t)t * stride, &st[t]);
     });
     for (unsigned t = 0; t < T; ++t)  // chunks are in call order: the first bad chunk has the first bad move
         if (st[t] != GWAOI_OK) return st[t];
-    HIP_TRY(w->last_error, hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(w->last_error, hipEventRecord(w->copy_ev, w->copy_st));
-    w->copy_pending = true;
-    w->stage_used[half] += words;
-    Run r = device_run(d, reinterpret_cast<const float *>(d + n), reinterpret_cast<const float *>(d + 2 * n), n);
-    r.dsp = with_space ? d + 3 * n : nullptr;
-    r.checked = true;
-    for (unsigned t = 0; t < T; ++t)
-        for (size_t sp = 0; sp < nsp; ++sp) {
-            const StageBox &b = boxes[(size_t)t * stride + sp];
-            if (!b.any) continue;
-            if (w->in_flight) {
-                w->deferred_boxes.push_back(DeferredBox{(uint32_t)sp, b.x0, b.z0, b.x1, b.z1});
-            } else {
-                note_pending_bbox(w->spaces[sp], b.x0, b.z0);
-                note_pending_bbox(w->spaces[sp], b.x1, b.z1);
-            }
-        }
+    if (int rc = send_staged(w, at, n, n, with_space, true, (with_space ? 4 : 3) * n, nullptr)) return rc;
+    for (unsigned t = 0; t < T; ++t) note_staged_boxes(w, boxes.data() + (size_t)t * stride, nsp);
+    return GWAOI_OK;
+}
+
+// A Moved batch in the caller's device memory (d_sp: a space per op, or nullptr to keep the slots').
+int queue_device_moves(gwaoi_world *w, const uint32_t *d_slots, const float *d_x, const float *d_z,
+                       const uint32_t *d_sp, size_t n) {
+    if (!n) return GWAOI_OK;
+    if (n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
+    if (w->dev_seq_pending) return GWAOI_ESTATE;
+    Run r = device_run(d_slots, d_x, d_z, n);
+    r.dsp = d_sp;
     queue_run(w, r);
+    return GWAOI_OK;
+}
+
+// gwaoi_moved_batch after its argument checks: host-checked, all of the batch or none of it.
+int moved_batch_host(gwaoi_world *w, const uint32_t *slots, const float *x, const float *z, size_t n) {
+    if (int rc = host_slots(w)) return rc;
+    // Batches of kStageMin+ moves go through pinned staging as one device batch (single-pass
+    // move apply); without room (or if the staging allocation failed) they queue as host ops.
+    if (n >= kStageMin && n <= 0xFFFFFFFFull - w->n_ops &&
+        w->staging.room(w->last_error, 4 * n, w->in_flight, nullptr) == GWAOI_OK)
+        return stage_moves(w, slots, x, z, n);
+    const uint32_t *space_of = w->space_of.data();
+    uint32_t sp;
+    for (size_t i = 0; i < n; ++i)
+        if (int rc = check_move(space_of, w->max_slots, slots[i], x[i], z[i], &sp)) return rc;
+    for (size_t i = 0; i < n; ++i)
+        submit(w, HostOp{HostOp::MOVED, slots[i], space_of[slots[i]], x[i], z[i], take_seq(w, nullptr)});
     return GWAOI_OK;
 }
 
@@ -1931,18 +1998,7 @@ int gwaoi_leave(gwaoi_world *w, uint32_t slot) {
     if (slot >= w->max_slots) return GWAOI_EBADSLOT;
     if (!w->alive[slot]) return GWAOI_ESTATE;
     if (w->dev_seq_pending) return GWAOI_ESTATE;
-    w->alive[slot] = 0;
-    w->spaces[w->space_of[slot]].alive--;
-    w->space_of[slot] = gw::SP_DEAD;
-    w->n_alive--;
-    if (w->sync) gw::sync_note_slot(w->sync, slot, gw::SP_DEAD);
-    w->space_ops_queued = true;
-    if (w->in_flight) {
-        defer(w, Deferred::LEAVE, slot, gw::SP_DEAD, 0.f, 0.f, w->seq_next);
-        return GWAOI_OK;
-    }
-    w->touched.push_back(slot);
-    push_host_op(w, slot, 0.f, 0.f, gw::SP_DEAD, w->seq_next);  // a Leave's seq is never compared
+    leave_valid(w, slot);
     return GWAOI_OK;
     });
 }
@@ -1974,7 +2030,9 @@ int gwaoi_enter_batch(gwaoi_world *w, uint32_t space, const uint32_t *slots, con
     }
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return GWAOI_ESTATE;
-    for (size_t i = 0; i < n; ++i) gwaoi_enter(w, space, slots[i], x[i], z[i]);
+    // (a slot in a space without AOI, which gwaoi_enter refuses and the validation above does not look for, is left out)
+    for (size_t i = 0; i < n; ++i)
+        if (!(w->sync && gw::sync_slot_plain(w->sync, slots[i]))) enter_valid(w, space, slots[i], x[i], z[i], nullptr);
     return GWAOI_OK;
     });
 }
@@ -1992,7 +2050,7 @@ int gwaoi_leave_batch(gwaoi_world *w, const uint32_t *slots, size_t n) {
     }
     std::sort(seen.begin(), seen.end());
     if (std::adjacent_find(seen.begin(), seen.end()) != seen.end()) return GWAOI_ESTATE;
-    for (size_t i = 0; i < n; ++i) gwaoi_leave(w, slots[i]);
+    for (size_t i = 0; i < n; ++i) leave_valid(w, slots[i]);
     return GWAOI_OK;
     });
 }
@@ -2002,18 +2060,7 @@ int gwaoi_moved_batch(gwaoi_world *w, const uint32_t *slots, const float *x, con
     if (!w || (n && (!slots || !x || !z))) return GWAOI_EINVAL;
     GW_LIVE(w);
     if (w->dev_seq_pending) return GWAOI_ESTATE;
-    if (int rc = host_slots(w)) return rc;
-    // Batches of kStageMin+ moves go through pinned staging as one device batch (single-pass
-    // move apply); without room (or if the staging allocation failed) they queue as host ops.
-    if (n >= kStageMin && n <= 0xFFFFFFFFull - w->n_ops && ensure_stage(w, 4 * n) == GWAOI_OK)
-        return stage_moves(w, slots, x, z, n);
-    for (size_t i = 0; i < n; ++i) {
-        if (slots[i] >= w->max_slots) return GWAOI_EBADSLOT;
-        if (!w->alive[slots[i]]) return GWAOI_ESTATE;
-        if (!finite2(x[i], z[i])) return GWAOI_ENONFINITE;
-    }
-    for (size_t i = 0; i < n; ++i) gwaoi_moved(w, slots[i], x[i], z[i]);
-    return GWAOI_OK;
+    return moved_batch_host(w, slots, x, z, n);
     });
 }
 
@@ -2022,11 +2069,7 @@ int gwaoi_moved_batch_device(gwaoi_world *w, const uint32_t *d_slots, const floa
     return gw::api_guard([&]() -> int {
     if (!w || (n && (!d_slots || !d_x || !d_z))) return GWAOI_EINVAL;
     GW_LIVE(w);
-    if (!n) return GWAOI_OK;
-    if (n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
-    if (w->dev_seq_pending) return GWAOI_ESTATE;
-    queue_run(w, device_run(d_slots, d_x, d_z, n));
-    return GWAOI_OK;
+    return queue_device_moves(w, d_slots, d_x, d_z, nullptr, n);
     });
 }
 
@@ -2105,22 +2148,11 @@ int gwaoi_moved_batch_stage(gwaoi_world *w, size_t n, uint32_t **slots, float **
     return gw::api_guard([&]() -> int {
     if (!w || !slots || !x || !z || n == 0 || n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
     GW_LIVE(w);
-    if (w->resv_n || w->dev_seq_pending) return GWAOI_ESTATE;
-    if (int rc = ensure_stage(w, 4 * n)) {
-        if (rc == 1) {
-            w->last_error = "staging memory holds this flush's batches: flush before staging more";
-            return GWAOI_ECAPACITY;
-        }
-        return rc;
-    }
-    const int h = w->stage_cur;
-    w->resv_half = h;
-    w->resv_n = n;
-    w->resv_h = w->h_stage[h] + w->stage_used[h];
-    w->resv_d = w->d_stage[h] + w->stage_used[h];
-    *slots = w->resv_h;
-    *x = reinterpret_cast<float *>(w->resv_h + n);
-    *z = reinterpret_cast<float *>(w->resv_h + 2 * n);
+    if (w->staging.resv_n || w->dev_seq_pending) return GWAOI_ESTATE;
+    if (int rc = w->staging.room(w->last_error, 4 * n, w->in_flight, "staging more")) return rc;
+    *slots = w->staging.reserve(n);
+    *x = reinterpret_cast<float *>(*slots + n);
+    *z = reinterpret_cast<float *>(*slots + 2 * n);
     return GWAOI_OK;
     });
 }
@@ -2129,12 +2161,12 @@ int gwaoi_moved_batch_commit(gwaoi_world *w, size_t k) {
     return gw::api_guard([&]() -> int {
     if (!w) return GWAOI_EINVAL;
     GW_LIVE(w);
-    const size_t n = w->resv_n;
+    MoveStaging &S = w->staging;
+    const size_t n = S.unreserve(), at = S.resv_at;
     if (!n || k > n) return n ? GWAOI_EINVAL : GWAOI_ESTATE;
-    w->resv_n = 0;
-    if (w->resv_half != w->stage_cur) return GWAOI_ESTATE;  // a flush launched in between took that half
+    if (S.resv_half != S.cur) return GWAOI_ESTATE;  // a flush launched in between took that half
     if (!k) return GWAOI_OK;
-    uint32_t *h = w->resv_h, *d = w->resv_d;
+    uint32_t *h = S.host(at);
     // After an Enter / Leave queued in this flush a slot's space may differ from its space at the
     // flush's start: the space column is filled (and the batch checked) on the host then.
     const bool with_space = w->space_ops_queued;
@@ -2144,26 +2176,9 @@ int gwaoi_moved_batch_commit(gwaoi_world *w, size_t k) {
         int st = GWAOI_OK;
         const float *hx = reinterpret_cast<const float *>(h + n), *hz = reinterpret_cast<const float *>(h + 2 * n);
         if (stage_chunk(w, h, hx, hz, n, 0, k, h, true, boxes.data(), &st) != k) return st;
-        for (size_t sp = 0; sp < boxes.size(); ++sp) {
-            const StageBox &b = boxes[sp];
-            if (!b.any) continue;
-            if (w->in_flight) {
-                w->deferred_boxes.push_back(DeferredBox{(uint32_t)sp, b.x0, b.z0, b.x1, b.z1});
-            } else {
-                note_pending_bbox(w->spaces[sp], b.x0, b.z0);
-                note_pending_bbox(w->spaces[sp], b.x1, b.z1);
-            }
-        }
+        note_staged_boxes(w, boxes.data(), boxes.size());
     }
-    const size_t words = (with_space ? 4 : 3) * n;
-    HIP_TRY(w->last_error, hipMemcpyAsync(d, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(w->last_error, hipEventRecord(w->copy_ev, w->copy_st));
-    w->copy_pending = true;
-    w->stage_used[w->resv_half] += 4 * n;
-    Run r = device_run(d, reinterpret_cast<const float *>(d + n), reinterpret_cast<const float *>(d + 2 * n), k);
-    r.dsp = with_space ? d + 3 * n : nullptr;
-    queue_run(w, r);
-    return GWAOI_OK;
+    return send_staged(w, at, n, k, with_space, false, 4 * n, nullptr);
     });
 }
 
@@ -2171,27 +2186,13 @@ int gwaoi_moved_batch_pinned(gwaoi_world *w, const uint32_t *slots, const float 
     return gw::api_guard([&]() -> int {
     if (!w || (n && (!slots || !x || !z)) || n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
     GW_LIVE(w);
-    if (w->dev_seq_pending || w->resv_n) return GWAOI_ESTATE;
+    if (w->dev_seq_pending || w->staging.resv_n) return GWAOI_ESTATE;
     if (!n) return GWAOI_OK;
     // after an Enter / Leave of this flush a slot's space may have changed: host-checked staging
-    if (w->space_ops_queued) return gwaoi_moved_batch(w, slots, x, z, n);
-    if (int rc = ensure_stage(w, 3 * n)) {
-        if (rc == 1) {
-            w->last_error = "staging memory holds this flush's batches: flush before queueing more";
-            return GWAOI_ECAPACITY;
-        }
-        return rc;
-    }
-    const int h = w->stage_cur;
-    uint32_t *d = w->d_stage[h] + w->stage_used[h];
-    HIP_TRY(w->last_error, hipMemcpyAsync(d, slots, n * sizeof(uint32_t), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(w->last_error, hipMemcpyAsync(d + n, x, n * sizeof(float), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(w->last_error, hipMemcpyAsync(d + 2 * n, z, n * sizeof(float), hipMemcpyHostToDevice, w->copy_st));
-    HIP_TRY(w->last_error, hipEventRecord(w->copy_ev, w->copy_st));
-    w->copy_pending = true;
-    w->stage_used[h] += 3 * n;
-    queue_run(w, device_run(d, reinterpret_cast<const float *>(d + n), reinterpret_cast<const float *>(d + 2 * n), n));
-    return GWAOI_OK;
+    if (w->space_ops_queued) return moved_batch_host(w, slots, x, z, n);
+    if (int rc = w->staging.room(w->last_error, 3 * n, w->in_flight, "queueing more")) return rc;
+    const void *const src[3] = {slots, x, z};
+    return send_staged(w, w->staging.fill(), n, n, false, false, 3 * n, src);
     });
 }
 
@@ -2255,13 +2256,7 @@ int world_queue_decoded(gwaoi_world *w, const uint32_t *d_slots, const float *d_
                         const uint32_t *d_sp, size_t n) {
     GW_LIVE(w);
     if (w->in_flight) return GWAOI_ESTATE;
-    if (!n) return GWAOI_OK;
-    if (n > 0xFFFFFFFFull - w->n_ops) return GWAOI_EINVAL;
-    if (w->dev_seq_pending) return GWAOI_ESTATE;
-    Run r = device_run(d_slots, d_x, d_z, n);
-    r.dsp = d_sp;
-    queue_run(w, r);
-    return GWAOI_OK;
+    return queue_device_moves(w, d_slots, d_x, d_z, d_sp, n);
 }
 
 }  // namespace gw
