@@ -7,8 +7,8 @@ this package holds its ctypes binding (``_lib``), the host-side mirror of the
 go-aoi interface (``aoi``), the seeded workloads (``workload``) and the
 in-tree build (``build``).
 """
-from ._lib import (CAST_DTYPE, CAST_NEIGHBORS, CAST_OWN, CAST_REC, NO_SLOT, STEER_FACE, STEER_MOVE, GwaoiError, Wire,  # noqa: F401
-                   World, load, pair_keys)
+from ._lib import (CAST_DTYPE, CAST_NEIGHBORS, CAST_OWN, CAST_REC, NO_SLOT, RANGE_PLANAR, RANGE_POINT, RANGE_QUERY,  # noqa: F401
+                   STEER_FACE, STEER_MOVE, GwaoiError, Wire, World, load, pair_keys)
 
 __all__ = ["World", "Wire", "GwaoiError", "load", "pair_keys", "CAST_REC", "CAST_DTYPE", "CAST_OWN",
-           "CAST_NEIGHBORS", "NO_SLOT", "STEER_MOVE", "STEER_FACE"]
+           "CAST_NEIGHBORS", "NO_SLOT", "STEER_MOVE", "STEER_FACE", "RANGE_QUERY", "RANGE_POINT", "RANGE_PLANAR"]

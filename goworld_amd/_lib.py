@@ -73,6 +73,7 @@ SYNC_EXPORTS = [
     "gwaoi_collect_client_switch", "gwaoi_neighbors_batch", "gwaoi_neighbors_batch_device",
     "gwaoi_related_batch", "gwaoi_related_batch_device", "gwaoi_entity_set_tag", "gwaoi_entity_set_tag_batch",
     "gwaoi_nearest_batch", "gwaoi_nearest_batch_device", "gwaoi_steer_batch", "gwaoi_steer_batch_device",
+    "gwaoi_range_batch", "gwaoi_range_batch_device", "gwaoi_range_count_batch", "gwaoi_range_count_batch_device",
 ]
 
 # every function include/gwaoi_wire.h declares
@@ -90,6 +91,10 @@ CAST_REC = 32      # ClientID[16] + msg, src slot, dst slot, 0 (uint32 little-en
 CAST_OWN, CAST_NEIGHBORS = 1, 2
 NO_SLOT = 0xFFFFFFFF  # gwaoi_nearest_batch: no neighbour passes the filter (GWAOI_NO_SLOT)
 STEER_MOVE, STEER_FACE = 1, 2  # gwaoi_steer_batch flags (GWAOI_STEER_MOVE / GWAOI_STEER_FACE)
+RANGE_POINT, RANGE_PLANAR = 1, 2  # gwaoi_range_query flags (GWAOI_RANGE_POINT / GWAOI_RANGE_PLANAR)
+# gwaoi_range_query, 32 B
+RANGE_QUERY = np.dtype([("center", "<u4"), ("flags", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
+                        ("radius", "<f4"), ("mask", "<u4"), ("want", "<u4")])
 CAST_DTYPE = np.dtype([("cid", np.uint8, (16,)), ("msg", "<u4"), ("src", "<u4"), ("dst", "<u4"), ("pad", "<u4")])
 
 
@@ -121,6 +126,10 @@ class GateRecords(C.Structure):
 
 class SlotRows(C.Structure):
     _fields_ = [("n", C.c_uint32), ("offsets", C.c_void_p), ("items", C.c_void_p)]
+
+
+class RangeRows(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("offsets", C.c_void_p), ("items", C.c_void_p), ("dists", C.c_void_p)]
 
 
 class WireGroups(C.Structure):
@@ -255,6 +264,10 @@ def load():
         "gwaoi_nearest_batch_device": ([vp, vp, vp, vp, sz, vp, vp], C.c_int),
         "gwaoi_steer_batch": ([vp, vp, vp, vp, vp, sz, vp, vp], C.c_int),
         "gwaoi_steer_batch_device": ([vp, vp, vp, vp, vp, sz, vp, vp], C.c_int),
+        "gwaoi_range_batch": ([vp, vp, sz, P(RangeRows)], C.c_int),
+        "gwaoi_range_batch_device": ([vp, vp, sz, P(RangeRows)], C.c_int),
+        "gwaoi_range_count_batch": ([vp, vp, sz, vp], C.c_int),
+        "gwaoi_range_count_batch_device": ([vp, vp, sz, vp], C.c_int),
         "gwaoi_wire_create": ([C.c_int, P(vp)], C.c_int),
         "gwaoi_wire_destroy": ([vp], None),
         "gwaoi_wire_last_error": ([vp], C.c_char_p),
@@ -802,6 +815,64 @@ class World:
         self._check(self._L.gwaoi_nearest_batch_device(self._w, q[0], q[1], q[2], n,
                                                        C.c_void_p(d_out_slot) if d_out_slot else None,
                                                        C.c_void_p(d_out_dist) if d_out_dist else None))
+
+    # ---- range reads (include/gwaoi_sync.h)
+    RANGE_POINT, RANGE_PLANAR = RANGE_POINT, RANGE_PLANAR
+
+    @staticmethod
+    def range_queries(centers, radii, masks=None, wants=None, points=None, planar=False) -> np.ndarray:
+        """A RANGE_QUERY array: query m asks for the entities within radii[m] of slot centers[m], or,
+        with points (n x 3: x, y, z) given, of points[m] in space centers[m].  radii, masks, wants and
+        planar broadcast over the queries; masks=None: everyone ((tag & mask) == want otherwise)."""
+        c = np.ascontiguousarray(np.atleast_1d(centers), np.uint32).reshape(-1)
+        q = np.zeros(c.size, RANGE_QUERY)
+        q["center"] = c
+        q["radius"] = np.broadcast_to(np.asarray(radii, np.float32), c.shape)
+        q["flags"] = np.where(np.broadcast_to(np.asarray(planar, bool), c.shape), RANGE_PLANAR, 0)
+        if points is not None:
+            pt = np.asarray(points, np.float32).reshape(-1, 3)
+            if pt.shape[0] != c.size:
+                raise ValueError(f"{c.size} spaces but {pt.shape[0]} points")
+            q["flags"] |= RANGE_POINT
+            q["x"], q["y"], q["z"] = pt[:, 0], pt[:, 1], pt[:, 2]
+        if masks is not None:
+            q["mask"] = np.broadcast_to(np.asarray(masks, np.uint32), c.shape)
+            q["want"] = np.broadcast_to(np.asarray(masks if wants is None else wants, np.uint32), c.shape)
+        return q
+
+    def range_batch(self, q):
+        """The entities within each query's radius on the frame of the last flush (gwaoi_range_batch):
+        (offsets[n + 1] uint32, items uint32, dists float32) copies; row m =
+        items[offsets[m]:offsets[m + 1]] in an unspecified order, dists parallel to items."""
+        a = np.ascontiguousarray(q, RANGE_QUERY).reshape(-1)
+        r = RangeRows()
+        self._check(self._L.gwaoi_range_batch(self._w, _p(a) if a.size else None, a.size, C.byref(r)))
+        off = np.ctypeslib.as_array(C.cast(r.offsets, C.POINTER(C.c_uint32)), shape=(r.n + 1,)).copy()
+        k = int(off[-1])
+        if not k:
+            return off, np.empty(0, np.uint32), np.empty(0, np.float32)
+        return (off, np.ctypeslib.as_array(C.cast(r.items, C.POINTER(C.c_uint32)), shape=(k,)).copy(),
+                np.ctypeslib.as_array(C.cast(r.dists, C.POINTER(C.c_float)), shape=(k,)).copy())
+
+    def range_count_batch(self, q) -> np.ndarray:
+        """The length of each query's row (gwaoi_range_count_batch): the count pass alone."""
+        a = np.ascontiguousarray(q, RANGE_QUERY).reshape(-1)
+        out = np.zeros(a.size, np.uint32)
+        self._check(self._L.gwaoi_range_count_batch(self._w, _p(a) if a.size else None, a.size,
+                                                    _p(out) if a.size else None))
+        return out
+
+    def range_batch_device(self, d_q: int, n: int):
+        """Queries in device memory (16-B aligned), rows stay in HBM: (offsets pointer, items pointer,
+        dists pointer, n_items), valid until the next range call.  n_items is offsets[n], read back."""
+        r = RangeRows()
+        self._check(self._L.gwaoi_range_batch_device(self._w, C.c_void_p(d_q) if d_q else None, n, C.byref(r)))
+        return r.offsets or 0, r.items or 0, r.dists or 0, _device_u32((r.offsets or 0) + 4 * r.n)
+
+    def range_count_batch_device(self, d_q: int, n: int, d_out: int):
+        """Queries and the n uint32 counts in device memory."""
+        self._check(self._L.gwaoi_range_count_batch_device(self._w, C.c_void_p(d_q) if d_q else None, n,
+                                                           C.c_void_p(d_out) if d_out else None))
 
     # ---- server-driven movement (include/gwaoi_sync.h)
     STEER_MOVE, STEER_FACE = STEER_MOVE, STEER_FACE

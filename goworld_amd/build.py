@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "lib", "libgwaoi.so")
 SOURCES = ["gwaoi_kernels.hip", "gwaoi_world.cpp", "gwaoi_strips.hip", "gwaoi_sync.hip", "gwaoi_wire.hip",
            "gwaoi_sparse.hip"]
-HEADERS = ["gwaoi_internal.h", "gwaoi_device.h", "gwaoi_mem.h", "gwaoi_plan.h", os.path.join("..", "..", "include", "gwaoi.h"),
+HEADERS = ["gwaoi_internal.h", "gwaoi_device.h", "gwaoi_mem.h", "gwaoi_plan.h", "gwaoi_range.h", os.path.join("..", "..", "include", "gwaoi.h"),
            os.path.join("..", "..", "include", "gwaoi_sync.h"),
            os.path.join("..", "..", "include", "gwaoi_strips.h"), os.path.join("..", "..", "include", "gwaoi_wire.h")]
 
@@ -108,6 +108,30 @@ def build_plan_test(force: bool = False, verbose: bool = False) -> str:
     return PLAN_TEST_OUT
 
 
+RANGE_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "range_test.cpp")
+RANGE_TEST_OUT = os.path.join(HERE, "lib", "range_test")
+
+
+def build_range_test(force: bool = False, verbose: bool = False, sanitize: bool = False) -> str:
+    """Stand-alone host test of csrc/gwaoi_range.h (a range read's window against its hit predicate): the
+    header alone, plain g++, the library's -ffp-contract=off.  sanitize: a second program with
+    -fsanitize=address,undefined (a host program of its own; nothing of it is loaded into Python)."""
+    out = RANGE_TEST_OUT + ("_san" if sanitize else "")
+    deps = [RANGE_TEST_SRC, os.path.join(CSRC, "gwaoi_range.h")]
+    if not force and os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
+        return out
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    tmp = out + ".tmp"
+    cmd = ["g++", "-std=c++17", "-O2", "-Wall", "-ffp-contract=off", "-fno-fast-math",
+           *(["-fsanitize=address,undefined", "-fno-sanitize-recover=all"] if sanitize else []),
+           "-I", CSRC, RANGE_TEST_SRC, "-o", tmp]
+    if verbose:
+        print(" ".join(cmd), file=sys.stderr)
+    subprocess.run(cmd, check=True)
+    os.replace(tmp, out)
+    return out
+
+
 TICK_BENCH_SRC =os.path.join(ROOT, "tools", "tick_bench.cpp")
 TICK_BENCH_OUT = os.path.join(HERE, "lib", "gwaoi_tick_bench")
 
@@ -136,3 +160,4 @@ if __name__ == "__main__":
     print(build_tick_bench(verbose=True))
     print(build_mem_test(verbose=True))
     print(build_plan_test(verbose=True))
+    print(build_range_test(verbose=True))

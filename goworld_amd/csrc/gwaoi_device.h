@@ -4,17 +4,9 @@
 #pragma once
 
 #include "gwaoi_internal.h"
+#include "gwaoi_range.h"  // cell_of: host and device, one function
 
 namespace gw {
-
-// Monotone non-decreasing in v (IEEE sub/mul round monotonically; clamp is
-// monotone).  keygen and every query use this one function.
-__device__ __forceinline__ int cell_of(float v, float o, float inv, uint32_t g) {
-    float t = (v - o) * inv;
-    t = fmaxf(t, 0.0f);
-    t = fminf(t, (float)(g - 1));
-    return (int)t;
-}
 
 __device__ __forceinline__ Rec16 ld_rec(const Rec16 *p, uint32_t i) {
     const uint4 q = reinterpret_cast<const uint4 *>(p)[i];

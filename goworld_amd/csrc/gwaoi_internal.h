@@ -415,8 +415,12 @@ struct WorldView {
     bool in_flight;         // gwaoi_tick_begin without its gwaoi_tick_finish yet
     const uint32_t *events; // last flush's events (device): [enters | leaves] as (a,b) pairs
     uint64_t n_enter, n_leave;
+    uint32_t max_spaces;
+    uint32_t n_grids;       // entries of F.grid the last flush wrote (a space created since has none)
 };
 WorldView world_view(gwaoi_world *w);
+// A space id that gwaoi_space_create returned and gwaoi_space_destroy has not taken back.
+bool world_space_used(gwaoi_world *w, uint32_t space);
 SyncState *&world_sync(gwaoi_world *w);
 // Buffers of the interest-set reads (gwaoi_sync.hip): the world's own, apart from the sync layer,
 // because the rows and membership reads must not create one.

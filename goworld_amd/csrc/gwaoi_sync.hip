@@ -1380,6 +1380,212 @@ __global__ __launch_bounds__(ST) void k_nearest(NearArgs A) {
     if (ln == 0 && werr) atomicOr(A.sc, werr);
 }
 
+// ------------------------------------------------------- range reads ------
+// The entities within a caller-chosen radius of an entity or of a point (gwaoi_range_batch): the
+// rows' shape (one wave per query, count / scan / write, no atomic per hit) over a window that is
+// not the go-aoi window and a centre that need not be a frame entry.  The window is centre -+
+// radius in the grid of the query's space, widened by range_window's margin (gwaoi_range.h;
+// it holds every hit), and may have any number of grid rows.  A candidate is tested
+// in two steps: the distance without dy from its frame record alone (never larger than the full
+// one, and the full one with GWAOI_RANGE_PLANAR), then only those lanes go on to the candidate's
+// slot, tag and y; the others re-read entry `clamp` (the centre's own, or entry 0 for a point).
+constexpr unsigned long long Q_E_INVAL = 1ull << 61;      // device forms: a flag bit outside the two, radius < 0
+constexpr unsigned long long Q_E_NONFINITE = 1ull << 60;  // device forms: a radius or point coordinate NaN or infinite
+constexpr unsigned long long Q_E_SPACE = 1ull << 59;      // device forms: a point's space id >= max_spaces
+constexpr unsigned long long RANGE_TOTAL = Q_E_SPACE - 1ull;
+constexpr uint32_t RANGE_NO_SELF = 0xFFFFFFFFu;  // a point query excludes nobody
+
+__device__ __forceinline__ float rflf(float v) { return __uint_as_float(rfl(__float_as_uint(v))); }
+
+// window_walk's walk over the cell rectangle W of grid gr: lane j loads row j's bounds, 64 rows at a
+// time, the rows are laid end to end and the wave reads 64 consecutive candidates per step, CAST_WU
+// steps with their loads in flight together.  step(b, q, live): lane ln's candidate of step u is
+// frame index b[u] with frame record q[u]; a lane past the window's end has live[u] false and
+// b[u] == clamp, a valid frame index (the frame is not empty).  The row layout (s_adj, s_mark) is
+// window_walk's, kept apart so that its users' code stays as it is: a fix to that scheme goes into both.
+template <class Step>
+__device__ __forceinline__ void range_walk(const FrameView &F, const SpaceGrid &gr, const RangeWindow &W, uint32_t clamp,
+                                           uint32_t w, uint32_t ln, Step &&step) {
+    __shared__ uint32_t s_adj[ST / 64][64];             // candidate index - position, per non-empty row
+    __shared__ uint32_t s_mark[ST / 64][CAST_WU * 64];  // a non-empty row starts at this position
+    const uint32_t *cs = F.cell_start;
+    const uint4 *frec = reinterpret_cast<const uint4 *>(F.rec);
+    const unsigned long long lt = (1ull << ln) - 1ull;
+    const unsigned long long le = ln == 63 ? ~0ull : (2ull << ln) - 1ull;
+    const uint32_t span = rfl((uint32_t)(W.cx1 - W.cx0) + 1u), nrows = rfl((uint32_t)(W.cz1 - W.cz0) + 1u);
+    const uint32_t row0 = rfl(gr.base + (uint32_t)W.cz0 * gr.gx + (uint32_t)W.cx0), gx = rfl(gr.gx);
+    for (uint32_t j0 = 0; j0 < nrows; j0 += 64u) {
+        // lane t: row j0 + t of the window, its candidates [jb, je)
+        const uint32_t t = j0 + ln;
+        const uint32_t rb = row0 + min(t, nrows - 1u) * gx;
+        const uint32_t jb = cs[rb], je = cs[rb + span];
+        const uint32_t len = t < nrows ? je - jb : 0u;
+        const uint32_t incl = wave_scan_add(len);
+        const uint32_t ex = incl - len, T = rdl(incl, 63);
+        const unsigned long long nem = __ballot(len != 0u);
+        if (len) s_adj[w][__popcll(nem & lt)] = jb - ex;
+        for (uint32_t p0 = 0; p0 < T; p0 += CAST_WU * 64u) {
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) s_mark[w][u * 64 + ln] = 0u;
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            if (len && ex >= p0 && ex - p0 < CAST_WU * 64u) s_mark[w][ex - p0] = 1u;
+            uint32_t nr = (uint32_t)__popcll(__ballot(len != 0u && ex < p0));  // non-empty rows started before this step
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            uint32_t b[CAST_WU];
+            uint4 q[CAST_WU];
+            bool live[CAST_WU];
+#pragma unroll
+            for (int u = 0; u < CAST_WU; ++u) {
+                const unsigned long long mk = __ballot(s_mark[w][u * 64 + ln] != 0u);
+                const uint32_t p = p0 + (uint32_t)u * 64u + ln;
+                const uint32_t row = nr + (uint32_t)__popcll(mk & le);  // rows started at or before p
+                nr += (uint32_t)__popcll(mk);
+                live[u] = p < T;
+                b[u] = live[u] ? p + s_adj[w][row - 1u] : clamp;  // (row >= 1 whenever p < T)
+                q[u] = frec[b[u]];
+            }
+            step(b, q, live);
+        }
+        __builtin_amdgcn_wave_barrier();  // s_adj is rewritten by the next row group
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    }
+}
+
+struct RangeArgs {
+    FrameView F;
+    SlotTab info;
+    const uint4 *slots;   // SLOT_U4 per slot (y)
+    const uint32_t *tag;  // per slot
+    const uint4 *q;       // two per query (gwaoi_range_query)
+    uint32_t n, max_slots, max_spaces;
+    uint32_t n_grids;     // entries of F.grid (a space created after the flush has none: an empty row)
+    uint32_t per;         // queries per block
+    uint32_t scan;        // cnt has n + 1 entries and is scanned next (else: the count form's n answers)
+    uint32_t *cnt;        // count pass: row lengths (cnt[n] = 0); scanned in place: the rows' offsets
+    unsigned long long *sc;  // items of all rows | Q_E_*
+    uint32_t *items;         // write pass
+    float *dists;            // parallel to items
+    unsigned long long cap;  // items either holds (the write pass writes nothing past a larger total)
+};
+
+template <bool WRITE>
+__device__ __forceinline__ void range_pass(const RangeArgs &A) {
+    __shared__ unsigned long long s_tot;
+    // queued behind the count pass and the scan (as rows_pass: the host regrows and relaunches)
+    if (WRITE && (*A.sc & RANGE_TOTAL) > A.cap) return;
+    const uint32_t blk = blockIdx.x, w = threadIdx.x / 64, ln = s_lane();
+    if (!WRITE) {
+        if (threadIdx.x == 0) s_tot = 0ull;
+        __syncthreads();
+    }
+    const float *sw = reinterpret_cast<const float *>(A.slots);
+    const unsigned long long lt = (1ull << ln) - 1ull;
+    unsigned long long wtot = 0ull, werr = 0ull;  // (wave-uniform)
+    const uint32_t m1 = min(A.n, (blk + 1u) * A.per);
+    for (uint32_t m = blk * A.per + w; m < m1; m += ST / 64) {
+        // the query record: one 32-B load per wave
+        const uint4 qa = A.q[2 * (size_t)m], qb = A.q[2 * (size_t)m + 1];
+        const uint32_t center = rfl(qa.x), fl = rfl(qa.y), mask = rfl(qb.z), want = rfl(qb.w);
+        const float px = __uint_as_float(rfl(qa.z)), py = __uint_as_float(rfl(qa.w)), pz = __uint_as_float(rfl(qb.x));
+        const float rad = __uint_as_float(rfl(qb.y));
+        const uint32_t base = WRITE ? rfl(A.cnt[m]) : 0u;
+        uint32_t run = 0;  // hits so far (wave-uniform)
+        const bool point = fl & GWAOI_RANGE_POINT, planar = fl & GWAOI_RANGE_PLANAR;
+        const float inf = __uint_as_float(0x7F800000u);
+        // (device forms only: the host forms are checked on the host)
+        unsigned long long e = 0ull;
+        if (fl & ~(GWAOI_RANGE_POINT | GWAOI_RANGE_PLANAR)) e |= Q_E_INVAL;
+        if (!(fabsf(rad) < inf)) e |= Q_E_NONFINITE;
+        else if (rad < 0.0f) e |= Q_E_INVAL;  // (-0.0 is 0)
+        if (point) {
+            if (!(fabsf(px) < inf && fabsf(py) < inf && fabsf(pz) < inf)) e |= Q_E_NONFINITE;
+            if (center >= A.max_spaces) e |= Q_E_SPACE;
+        } else if (center >= A.max_slots) {
+            e |= Q_E_SLOT;
+        }
+        werr |= e;
+        // the centre, its space and the entry idle lanes re-read; an empty frame has no entry at all
+        bool go = !e && A.F.n != 0u;
+        uint32_t sp = 0u, self = RANGE_NO_SELF, clamp = 0u;
+        float cx = px, cy = py, cz = pz;
+        if (go && point) {
+            sp = center;
+            go = sp < A.n_grids;
+        } else if (go) {
+            const uint32_t r0 = rfl(A.info.rank[center]);  // (rank: 0xFFFFFFFF if never live)
+            go = r0 < A.F.n;
+            if (go) {
+                const SlotSp S0 = ld_ss(A.F.ss, r0);
+                const Rec16 R = ld_rec(A.F.rec, r0);
+                go = rfl(S0.slot) == center;  // (else it left the frame: nilSpace or a space without AOI)
+                sp = rfl(S0.sp);
+                cx = rflf(R.x);
+                cz = rflf(R.z);
+                cy = rflf(sw[SLOT_W * (size_t)center + POS_Y]);
+                self = clamp = r0;
+            }
+        }
+        if (go) {
+            const SpaceGrid gr = A.F.grid[sp];
+            const RangeWindow W = range_window(cx, cz, rad, gr.ox, gr.oz, gr.inv, gr.gx, gr.gz);
+            range_walk(A.F, gr, W, clamp, w, ln, [&](const uint32_t(&b)[CAST_WU], const uint4(&q)[CAST_WU], const bool(&live)[CAST_WU]) {
+                bool pre[CAST_WU];
+                uint32_t ds[CAST_WU], tg[CAST_WU];
+                float y[CAST_WU], dp[CAST_WU];
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) {
+                    // without dy: fl(fl(a + b) + c) >= fl(a + c) for b >= 0, so no hit fails this
+                    const float dx = __uint_as_float(q[u].x) - cx, dz = __uint_as_float(q[u].y) - cz;
+                    dp[u] = range_dist(range_d2(dx, 0.0f, dz, true));
+                }
+                keep_loads(dp);  // (both steps' square roots, then both slot loads: no branch around either)
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) {
+                    pre[u] = live[u] && b[u] != self && dp[u] <= rad;
+                    ds[u] = ld_ss(A.F.ss, pre[u] ? b[u] : clamp).slot;
+                }
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) {
+                    tg[u] = A.tag[ds[u]];
+                    y[u] = sw[SLOT_W * (size_t)ds[u] + POS_Y];
+                }
+                keep_loads(tg);  // (issued together for both steps, not under the later step's hit branch)
+                keep_loads(y);
+#pragma unroll
+                for (int u = 0; u < CAST_WU; ++u) {
+                    float dist;
+                    const bool in = range_hit(cx, cy, cz, __uint_as_float(q[u].x), y[u], __uint_as_float(q[u].y), planar, rad, &dist);
+                    const bool hit = pre[u] && in && (tg[u] & mask) == want;
+                    const unsigned long long hb = __ballot(hit);
+                    const uint32_t p = base + run + (uint32_t)__popcll(hb & lt);
+                    run += (uint32_t)__popcll(hb);
+                    if (WRITE && hit && p < A.cap) {
+                        A.items[p] = ds[u];
+                        A.dists[p] = dist;
+                    }
+                }
+            });
+        }
+        if (!WRITE) {
+            if (ln == 0) A.cnt[m] = run;  // once per query
+            wtot += run;
+        }
+    }
+    if (WRITE) return;
+    if (ln == 0 && wtot) atomicAdd(&s_tot, wtot);
+    if (ln == 0 && werr) atomicOr(A.sc, werr);  // (one lane per wave that saw a bad query)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_tot) atomicAdd(A.sc, s_tot);         // one per block
+        if (blk == 0 && A.scan) A.cnt[A.n] = 0u;  // the scan's last entry becomes the (32-bit) total
+    }
+}
+
+__global__ __launch_bounds__(ST) void k_range_count(RangeArgs A) { range_pass<false>(A); }
+__global__ __launch_bounds__(ST) void k_range_write(RangeArgs A) { range_pass<true>(A); }
+
 // ------------------------------------------------ server-driven movement ------
 // Monster.Tick's chase and FaceTo (Monster.go:80-102, Entity.go:1292-1304, Vector3.go:44-77) for a
 // batch of (mover, target, step, flags) messages: one lane per message, k_related's gate (two rank
@@ -2562,6 +2768,10 @@ struct QueryState {
     PinnedBuf<unsigned long long> h_sc;
     PinnedBuf<uint32_t> h_off, h_items;  // the host form's rows
     DevBuf<uint32_t> out;            // the host forms' membership / nearest answers on the device
+    // range reads: results of their own (valid until the next range call, whatever the rows calls do)
+    DevBuf<uint32_t> r_cnt, r_items;
+    DevBuf<float> r_dists;
+    PinnedBuf<uint32_t> h_roff, h_ritems, h_rdists;  // (h_rdists holds floats)
 };
 
 void query_destroy(QueryState *Q) { delete Q; }  // (the world has synchronised its streams)
@@ -2789,6 +2999,144 @@ int query_nearest(gwaoi_world *w, const uint32_t *slots, const uint32_t *masks, 
         return GWAOI_EBADSLOT;
     }
     return GWAOI_OK;
+}
+
+int range_status(gwaoi_world *w, unsigned long long sc) {
+    if (!(sc & ~RANGE_TOTAL)) return GWAOI_OK;
+    world_set_error(w, "range: rows of queries with a bad slot, space, flag, radius or point are empty");
+    return (sc & Q_E_SLOT) ? GWAOI_EBADSLOT : (sc & Q_E_SPACE) ? GWAOI_EBADSPACE : (sc & Q_E_INVAL) ? GWAOI_EINVAL : GWAOI_ENONFINITE;
+}
+
+// gwaoi_range_batch / gwaoi_range_count_batch (_device): the frame, the tags and the slots' y (the
+// sync layer's).  out == nullptr is the count form: the count pass alone, its n answers in counts.
+int query_range(gwaoi_world *w, const gwaoi_range_query *q, size_t n, gwaoi_range_rows *out, uint32_t *counts,
+                bool count_only, bool on_device) {
+    if (!w || (count_only ? (n && !counts) : !out) || (n && !q)) return GWAOI_EINVAL;
+    SyncState *S;
+    if (int rc = state(w, &S)) return rc;
+    const WorldView v = world_view(w);
+    if (v.pending_ops) return GWAOI_ESTATE;
+    if (n > 0x7FFFFFFFull) return GWAOI_EINVAL;
+    if (on_device) {
+        if (n && (reinterpret_cast<uintptr_t>(q) & 15u)) return GWAOI_EINVAL;  // (two 16-B loads per query)
+    } else {  // nothing is produced on error: checked before any device work
+        for (size_t m = 0; m < n; ++m) {
+            const gwaoi_range_query &x = q[m];
+            if (x.flags & ~(GWAOI_RANGE_POINT | GWAOI_RANGE_PLANAR)) return GWAOI_EINVAL;
+            if (!std::isfinite(x.radius)) return GWAOI_ENONFINITE;
+            if (x.radius < 0.0f) return GWAOI_EINVAL;  // (-0.0 is 0)
+            if (x.flags & GWAOI_RANGE_POINT) {
+                if (!std::isfinite(x.x) || !std::isfinite(x.y) || !std::isfinite(x.z)) return GWAOI_ENONFINITE;
+                if (!world_space_used(w, x.center)) return GWAOI_EBADSPACE;
+            } else if (x.center >= v.max_slots) {
+                return GWAOI_EBADSLOT;
+            }
+        }
+    }
+    if (n && (unsigned long long)n * v.F.n > RANGE_TOTAL) {  // (the total shares its word with the error bits)
+        world_set_error(w, "range: more queries times entities than the total can count");
+        return GWAOI_ECAPACITY;
+    }
+    QueryState *Q;
+    if (int rc = query_state(w, &Q)) return rc;
+    RangeArgs A{};
+    if (n) {
+        if (int rc = push(S)) return rc;  // every earlier tag and position write is visible
+        A.F = v.F;
+        A.info = v.info;
+        A.slots = S->slots;
+        A.tag = S->tag;
+        if (on_device) {
+            A.q = reinterpret_cast<const uint4 *>(q);
+        } else {
+            if (int rc = q_ensure(w, Q->in, 8 * n)) return rc;
+            HIP_TRY(w, hipMemcpyAsync(Q->in, q, n * sizeof(gwaoi_range_query), hipMemcpyHostToDevice, v.st));
+            A.q = reinterpret_cast<const uint4 *>(Q->in.get());
+        }
+        A.n = (uint32_t)n;
+        A.max_slots = v.max_slots;
+        A.max_spaces = v.max_spaces;
+        A.n_grids = v.n_grids;
+        A.per = query_chunk(n);
+        A.sc = Q->sc;
+    }
+    const uint32_t nb = n ? cdivu(n, A.per) : 0u;
+    if (count_only) {  // one launch, one host wait, one copy
+        if (!n) return GWAOI_OK;
+        if (!on_device)
+            if (int rc = q_ensure(w, Q->out, n)) return rc;
+        A.cnt = on_device ? counts : Q->out.get();
+        A.scan = 0u;
+        HIP_TRY(w, hipMemsetAsync(Q->sc, 0, 8, v.st));
+        k_range_count<<<nb, ST, 0, v.st>>>(A);
+        HIP_TRY(w, hipGetLastError());
+        if (!on_device) HIP_TRY(w, hipMemcpyAsync(counts, A.cnt, n * 4, hipMemcpyDeviceToHost, v.st));
+        unsigned long long sc;
+        if (int rc = query_sc(w, Q, v.st, &sc)) return rc;
+        return range_status(w, sc);
+    }
+    if (int rc = q_ensure(w, Q->r_cnt, n + 1)) return rc;
+    if (int rc = q_ensure(w, Q->r_items, 1)) return rc;  // (an empty result's pointers)
+    if (int rc = q_ensure(w, Q->r_dists, 1)) return rc;
+    uint64_t total = 0;
+    int status = GWAOI_OK;
+    if (n) {
+        A.cnt = Q->r_cnt;
+        A.scan = 1u;
+        if (int rc = q_ensure(w, Q->scan_tmp, scan_tmp_elems(n + 1) + 4)) return rc;
+        HIP_TRY(w, hipMemsetAsync(Q->sc, 0, 8, v.st));
+        k_range_count<<<nb, ST, 0, v.st>>>(A);
+        HIP_TRY(w, hipGetLastError());
+        scan_exclusive(Q->r_cnt, Q->r_cnt, n + 1, Q->scan_tmp, v.st);
+        // the write pass is queued with the outputs as they are (the last call's size) before the one
+        // host wait, which brings the total and the device form's error bits
+        A.items = Q->r_items;
+        A.dists = Q->r_dists;
+        A.cap = std::min(Q->r_items.cap(), Q->r_dists.cap());
+        k_range_write<<<nb, ST, 0, v.st>>>(A);
+        HIP_TRY(w, hipGetLastError());
+        unsigned long long sc;
+        if (int rc = query_sc(w, Q, v.st, &sc)) return rc;
+        status = range_status(w, sc);
+        total = sc & RANGE_TOTAL;
+        if (total > 0xFFFFFFFFull) {
+            world_set_error(w, "range: rows of more than 2^32 - 1 items");
+            return GWAOI_ECAPACITY;
+        }
+        if (total > A.cap) {  // (the write pass declined: items and dists regrow together)
+            if (int rc = q_ensure(w, Q->r_items, total)) return rc;
+            if (int rc = q_ensure(w, Q->r_dists, total)) return rc;
+            A.items = Q->r_items;
+            A.dists = Q->r_dists;
+            A.cap = std::min(Q->r_items.cap(), Q->r_dists.cap());
+            k_range_write<<<nb, ST, 0, v.st>>>(A);
+            HIP_TRY(w, hipGetLastError());
+            if (on_device) HIP_TRY(w, hipStreamSynchronize(v.st));  // (the rows are complete on return)
+        }
+    } else {
+        HIP_TRY(w, hipMemsetAsync(Q->r_cnt, 0, 4, v.st));
+        if (on_device) HIP_TRY(w, hipStreamSynchronize(v.st));
+    }
+    out->n = (uint32_t)n;
+    if (on_device) {
+        out->offsets = Q->r_cnt;
+        out->items = Q->r_items;
+        out->dists = Q->r_dists;
+    } else {
+        if (int rc = q_ensure_host(w, Q->h_roff, n + 1)) return rc;
+        if (int rc = q_ensure_host(w, Q->h_ritems, std::max<uint64_t>(total, 1))) return rc;
+        if (int rc = q_ensure_host(w, Q->h_rdists, std::max<uint64_t>(total, 1))) return rc;
+        HIP_TRY(w, hipMemcpyAsync(Q->h_roff, Q->r_cnt, (n + 1) * 4, hipMemcpyDeviceToHost, v.st));
+        if (total) {
+            HIP_TRY(w, hipMemcpyAsync(Q->h_ritems, Q->r_items, total * 4, hipMemcpyDeviceToHost, v.st));
+            HIP_TRY(w, hipMemcpyAsync(Q->h_rdists, Q->r_dists, total * 4, hipMemcpyDeviceToHost, v.st));
+        }
+        HIP_TRY(w, hipStreamSynchronize(v.st));
+        out->offsets = Q->h_roff;
+        out->items = Q->h_ritems;
+        out->dists = reinterpret_cast<const float *>(Q->h_rdists.get());
+    }
+    return status;
 }
 
 int set_tags(gwaoi_world *w, const uint32_t *slots, const uint32_t *tags, size_t n) {
@@ -3042,6 +3390,22 @@ int gwaoi_nearest_batch_device(gwaoi_world *w, const uint32_t *d_slots, const ui
     return gw::api_guard([&]() -> int {
     return gw::query_nearest(w, d_slots, d_masks, d_wants, n, d_out_slot, d_out_dist, true);
     });
+}
+
+int gwaoi_range_batch(gwaoi_world *w, const gwaoi_range_query *q, size_t n, gwaoi_range_rows *out) {
+    return gw::api_guard([&]() -> int { return gw::query_range(w, q, n, out, nullptr, false, false); });
+}
+
+int gwaoi_range_batch_device(gwaoi_world *w, const gwaoi_range_query *d_q, size_t n, gwaoi_range_rows *out) {
+    return gw::api_guard([&]() -> int { return gw::query_range(w, d_q, n, out, nullptr, false, true); });
+}
+
+int gwaoi_range_count_batch(gwaoi_world *w, const gwaoi_range_query *q, size_t n, uint32_t *out_counts) {
+    return gw::api_guard([&]() -> int { return gw::query_range(w, q, n, nullptr, out_counts, true, false); });
+}
+
+int gwaoi_range_count_batch_device(gwaoi_world *w, const gwaoi_range_query *d_q, size_t n, uint32_t *d_out_counts) {
+    return gw::api_guard([&]() -> int { return gw::query_range(w, d_q, n, nullptr, d_out_counts, true, true); });
 }
 
 int gwaoi_steer_batch(gwaoi_world *w, const uint32_t *movers, const uint32_t *targets, const float *steps,

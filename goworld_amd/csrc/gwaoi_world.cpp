@@ -2232,8 +2232,12 @@ WorldView world_view(gwaoi_world *w) {
     v.events = last_events(w);
     v.n_enter = w->last_n_enter;
     v.n_leave = w->last_n_leave;
+    v.max_spaces = w->max_spaces;
+    v.n_grids = (uint32_t)w->fr[w->cur].hgrid.size();
     return v;
 }
+
+bool world_space_used(gwaoi_world *w, uint32_t space) { return space < w->n_space_ids && w->spaces[space].used; }
 
 SyncState *&world_sync(gwaoi_world *w) { return w->sync; }
 QueryState *&world_query(gwaoi_world *w) { return w->query; }

@@ -51,7 +51,7 @@
 extern "C" {
 #endif
 
-#define GWAOI_ABI_VERSION 6  /* 6: gwaoi_debug.overlapped_flushes (and, additive within 6, gwaoi_collect_broadcast(_device) and gwaoi_steer_batch(_device) in gwaoi_sync.h); 5: GWAOI_F_TEST_* flags replace environment switches, GWAOI_F_BATCH_READY ignored */
+#define GWAOI_ABI_VERSION 6  /* 6: gwaoi_debug.overlapped_flushes (and, additive within 6, gwaoi_collect_broadcast(_device), gwaoi_steer_batch(_device) and gwaoi_range_batch / gwaoi_range_count_batch(_device) in gwaoi_sync.h); 5: GWAOI_F_TEST_* flags replace environment switches, GWAOI_F_BATCH_READY ignored */
 
 typedef struct gwaoi_world gwaoi_world;
 

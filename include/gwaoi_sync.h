@@ -38,6 +38,10 @@
  *     Normalized(target - mypos) * step)  examples/unity_demo/Monster.go:80-102
  *   Entity.FaceTo / FaceToPos           Entity.go:1292-1304       (GWAOI_STEER_MOVE, GWAOI_STEER_FACE)
  *     Vector3.DirToYaw / Normalize      Vector3.go:44-77
+ *   Monster.AI's range test: DistanceTo(monster) >             gwaoi_range_batch(_device),
+ *     GetAttackRange()  examples/unity_demo/Monster.go:72,108     gwaoi_range_count_batch(_device)
+ *     and Monster.attack (Monster.go:143-151) for everyone in     (DistanceTo <= r about an entity or
+ *     range instead of one player                                   a point)
  *
  * Entity ids and client ids are the reference's 16-byte strings
  * (common.ENTITYID_LENGTH = common.CLIENTID_LENGTH = uuid.UUID_LENGTH = 16,
@@ -330,6 +334,79 @@ int gwaoi_nearest_batch(gwaoi_world *w, const uint32_t *slots, const uint32_t *m
 /* Same; every array in device memory, the outputs complete on return. */
 int gwaoi_nearest_batch_device(gwaoi_world *w, const uint32_t *d_slots, const uint32_t *d_masks,
                                const uint32_t *d_wants, size_t n, uint32_t *d_out_slot, float *d_out_dist);
+
+/* ---- range reads ------------------------------------------------------------ */
+/* The entities within a caller-chosen radius of an entity or of a point, for a batch of queries on
+ * the GPU: an area attack about a monster (Monster.attack, Monster.go:143-151, hits one player
+ * inside GetAttackRange() = 3, Monster.go:72,108; this is everyone inside it), an aggro radius
+ * smaller than the AOI distance, a trigger zone about a point where nobody stands, a count of
+ * players within r.  (TODO.md:19 asks for distances other than the space's one; this is the read,
+ * the relation itself keeps the space's distance.)
+ *
+ * Candidates.  Every entity of the frame of the last committed flush that is in the query's space:
+ * the centre slot's space, or `center` itself with GWAOI_RANGE_POINT.  The go-aoi relation plays no
+ * part: an entity three AOI distances away is found if the radius reaches it.  A slot-centred query
+ * never has its centre in its row; a point query has an entity standing exactly on the point in its
+ * row.  Entities in nilSpace or in a space without AOI are not in the frame and are never found.  A
+ * slot-centred query whose centre is outside the frame (never entered, left, nilSpace, a space
+ * without AOI) has an empty row; that is not an error, as for gwaoi_neighbors_batch.  A space
+ * created since the last flush has nobody in the frame: an empty row.
+ * Distance.  Vector3.DistanceTo exactly as gwaoi_nearest_batch defines it: dx = b.x - c.x, likewise
+ * dy and dz, d2 = fl32(fl32(fl32(dx*dx) + fl32(dy*dy)) + fl32(dz*dz)), no fused step, denormals
+ * kept, dist = (float)sqrt((double)d2).  A candidate's x and z are the frame's, its y the slot's
+ * position record.  Without POINT the centre's x and z are its frame record and its y its slot
+ * record; with POINT the centre is (x, y, z) of the query.  With GWAOI_RANGE_PLANAR the dy*dy term
+ * is left out: d2 = fl32(fl32(dx*dx) + fl32(dz*dz)), a cylinder.
+ * Hit.  A candidate is a hit iff dist <= radius, compared in float32 (Go's e.DistanceTo(o) <= r:
+ * the bound is inclusive), and (tag[b] & mask) == want (gwaoi_entity_set_tag; mask = want = 0:
+ * everyone).  dists[] holds that dist.
+ * Order.  The order within a row is unspecified, as for gwaoi_neighbors_batch; the set and every
+ * distance are exact.  items and dists are parallel.
+ * Count.  The _count_ forms give counts[m] = offsets[m+1] - offsets[m] and run the count pass only.
+ * State.  GWAOI_ESTATE with ops queued or a flush in flight, as for the interest-set reads.  No side
+ * effects: a query made twice gives the same answer.  offsets, items and dists are world-owned and
+ * valid until the next range call (of either form).  n == 0 gives out->n == 0, a
+ * one-entry offsets and GWAOI_OK.  More than 2^32 - 1 items give GWAOI_ECAPACITY.
+ * Errors, host forms (nothing is produced, everything is checked before any device work): a null
+ * world or output, or a null query array with n > 0: GWAOI_EINVAL; a flag bit outside the two:
+ * GWAOI_EINVAL; radius < 0: GWAOI_EINVAL (-0.0 is 0); a NaN or infinite radius: GWAOI_ENONFINITE; a
+ * NaN or infinite point coordinate with POINT: GWAOI_ENONFINITE; a slot >= max_slots:
+ * GWAOI_EBADSLOT; an unknown or destroyed space with POINT: GWAOI_EBADSPACE (a valid space with
+ * nobody in it gives an empty row and GWAOI_OK).
+ * Errors, device forms (d_q in device memory of the world's GPU, 16-B aligned, read before the call
+ * returns; a misaligned d_q is GWAOI_EINVAL): the offending query gets an empty row (count 0),
+ * every other answer is delivered, the world stays usable and the call returns the matching code
+ * (the broadcast's device-form convention).  A space id >= max_spaces is the only bad space the
+ * device sees; an id below it that names no space has nobody in it.  When several classes occur in
+ * one call, the code of any one of them comes back.
+ * Cost.  One wave per query; the time follows the candidates in the cells the radius covers.  A
+ * radius that spans a whole large space is correct and slow. */
+#define GWAOI_RANGE_POINT  1u  /* center is a space id, (x, y, z) the centre; else center is a slot */
+#define GWAOI_RANGE_PLANAR 2u  /* drop dy: d2 = fl32(fl32(dx*dx) + fl32(dz*dz)) (a cylinder) */
+
+typedef struct {          /* 32 B */
+    uint32_t center;      /* slot, or space id with GWAOI_RANGE_POINT */
+    uint32_t flags;
+    float x, y, z;        /* the point; ignored without GWAOI_RANGE_POINT */
+    float radius;
+    uint32_t mask, want;  /* a hit also needs (tag[b] & mask) == want; 0, 0: everyone */
+} gwaoi_range_query;
+
+typedef struct {
+    uint32_t n;
+    const uint32_t *offsets; /* n + 1 entries; row m = items[offsets[m] .. offsets[m+1]) */
+    const uint32_t *items;   /* slots */
+    const float *dists;      /* parallel to items */
+} gwaoi_range_rows;
+
+int gwaoi_range_batch(gwaoi_world *w, const gwaoi_range_query *q, size_t n, gwaoi_range_rows *out);
+/* Same; d_q in device memory, offsets, items and dists stay in device memory (offsets[n], the
+ * number of items, included).  One host wait unless the items outgrew the last call's. */
+int gwaoi_range_batch_device(gwaoi_world *w, const gwaoi_range_query *d_q, size_t n, gwaoi_range_rows *out);
+/* out_counts[m] = the length of row m (n entries of the caller's). */
+int gwaoi_range_count_batch(gwaoi_world *w, const gwaoi_range_query *q, size_t n, uint32_t *out_counts);
+/* Same; d_q and d_out_counts in device memory, complete on return. */
+int gwaoi_range_count_batch_device(gwaoi_world *w, const gwaoi_range_query *d_q, size_t n, uint32_t *d_out_counts);
 
 /* ---- server-driven movement ------------------------------------------------- */
 /* Monster.Tick's step for a batch of n entities (Monster.go:80-102): move toward a target and face
