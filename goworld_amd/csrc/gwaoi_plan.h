@@ -39,6 +39,9 @@ struct FlushFacts {
     bool ovl_ok;    // a speculative launch
     bool mid_last;  // the previous flush recorded its set's mid event
     bool gen_same;  // nothing but that flush was queued on the stream since its launch (gen == gen_launch)
+    // that flush's special pass rode on its sort (its plan's sp_fused; true when no flush preceded): it
+    // has read keygen's special-tile flags before its mid event
+    bool prev_sp_fused;
     // ---- grid
     uint32_t total_cells;
     bool prev_grid_same;   // the previous frame was cut with this flush's grid (cells and every space's grid)
@@ -93,8 +96,10 @@ inline FlushPlan plan_flush(const FlushFacts &f) {
     p.grid_same = f.frame_grid_same;
     p.incr = flush_incr(f);
     // Overlap (speculative launches): only when nothing else was queued on the stream since the
-    // previous flush's launch, and with no stage timing but the combined pass's.
-    p.ovl = f.ovl_ok && f.mid_last && f.gen_same && p.incr && f.n_prev > 0 &&
+    // previous flush's launch, and with no stage timing but the combined pass's.  The early kernels
+    // rewrite the world's one special-tile flag array (keygen), which the previous flush's special
+    // pass reads: behind its mid event unless it was fused, so only a fused flush may be overlapped.
+    p.ovl = f.ovl_ok && f.mid_last && f.gen_same && f.prev_sp_fused && p.incr && f.n_prev > 0 &&
             (f.timing_mask & ~(1u << ST_COMBINED)) == 0 && !f.check_stages;
 #ifdef GWAOI_EXP_NO_OVERLAP
     p.ovl = false;  // diagnostics build only: one flush at a time (the A/B of the overlap)

@@ -320,6 +320,9 @@ struct gwaoi_world {
     gw::SlotTab sinfo{};
     // incremental frame sort (grid unchanged): per-cell counts, arrival lists
     gw::DevBuf<unsigned long long> cnt64, scan64_tmp;
+    // scan tiles of the last incremental sort: scan64_tmp is laid out by them ([entries per tile |
+    // changed cells per tile]), and only the first half is left zero (flush_keys_sort)
+    uint32_t incr_tiles = 0;
     gw::DevBuf<uint32_t> arr_pos, arr_idx;
     gw::DevBuf<uint32_t> coll;  // slots moved twice in one flush (single-pass apply)
     gw::DevBuf<uint32_t> special;  // per previous-frame tile: keygen saw a special entity (the special pass's skip list)
@@ -423,9 +426,10 @@ struct gwaoi_world {
     bool in_flight = false;
     struct Flight {
         // how it was launched: its set, frames, seq floor and entries, and every decision of it.
-        // plan.sp_fused records whether its special pass rode on the sort; nothing reads that yet
-        // ("The flush plan": known gap)
+        // plan.sp_fused (its special pass rode on the sort) is the next flush's prev_sp_fused: when
+        // that flush is planned, fl still is this flight
         gw::FlushPlan plan;
+        bool launched = false;  // a flush was launched (else plan holds nothing)
         uint64_t seq_next;  // seq_next when the flush's queue was closed (the next flush's floor)
         bool dev_seq;       // it held an explicit-seq device batch
         EvCaps cap;         // event capacities its pair passes were launched with (writes clipped to them)
@@ -930,6 +934,7 @@ gw::FlushFacts flush_facts(gwaoi_world *w, const DevFrame &P, const DevFrame &Fn
     f.dev_struct = w->dev_struct; f.unique_moves = w->unique_moves; f.have_bucketed = w->mv_binned != nullptr;
     f.force_radix = w->force_radix; f.force_copy = w->force_copy; f.check_stages = w->check_stages;
     f.timing_mask = w->timing_mask; f.ovl_ok = w->ovl_ok; f.mid_last = w->mid_last;
+    f.prev_sp_fused = !w->fl.launched || w->fl.plan.sp_fused;  // (fl: the flush launched last)
     const uint32_t ns = std::max(1u, w->n_space_ids);
     auto cut_with = [&](const DevFrame &fr) {
         return fr.hgrid.size() == ns && !std::memcmp(fr.hgrid.data(), w->h_grid, ns * sizeof(SpaceGrid));
@@ -967,8 +972,10 @@ int flush_ensure(gwaoi_world *w, FlushSet &S, DevFrame &Fn, const gw::FlushFacts
 // early kernels (its set's mid_ev), while that flush's pair passes and finish still run on the
 // stream; this flush's pair passes wait for its own early kernels.  Nothing the early kernels touch
 // is read or written by the previous flush's pair passes or finish: the scratch, tile totals and
-// boxes are per set, the frames rotate over three, and the special pass rides on the arrival launch
-// (it reads the previous frame early).
+// boxes are per set, the frames rotate over three, and the one world-level array both touch, keygen's
+// special-tile flags, that flush has read already: the plan overlaps only a flush whose special pass
+// rode on its sort's arrival launch (prev_sp_fused; DESIGN.md, "The flush plan", lists every
+// world-level buffer).
 int flush_open(gwaoi_world *w, DevFrame &Fn, const gw::FlushPlan &plan, hipStream_t *st) {
     if (plan.ovl) {
         *st = w->early_st;
@@ -979,6 +986,14 @@ int flush_open(gwaoi_world *w, DevFrame &Fn, const gw::FlushPlan &plan, hipStrea
         const uint32_t ns = std::max(1u, w->n_space_ids);
         HIP_TRY(w->last_error, hipMemcpyAsync(Fn.grid, w->h_grid, sizeof(SpaceGrid) * ns, hipMemcpyHostToDevice, *st));
         Fn.hgrid.assign(w->h_grid.get(), w->h_grid + ns);
+    }
+    // The incremental sort leaves its scratch as [zeros | the changed-cell counts of its scan tiles].
+    // Laid out for another number of tiles, those counts would lie where keygen adds its entries per
+    // tile: zero the scratch again, once per such grid change (the flush behind a non-incremental one).
+    if (plan.incr && gw::incr_sort_tiles(Fn.total_cells) != w->incr_tiles) {
+        HIP_TRY(w->last_error, hipMemsetAsync(w->scan64_tmp, 0, gw::incr_sort_tmp_elems(Fn.total_cells) *
+                                                                    sizeof(unsigned long long), *st));
+        w->incr_tiles = gw::incr_sort_tiles(Fn.total_cells);
     }
     // the staged move batches' H2D copies (copy stream) land before the flush reads them
     return w->staging.wait(w->last_error, *st);
@@ -1181,6 +1196,7 @@ int record_flight(gwaoi_world *w, FlushSet &S, const gw::FlushPlan &plan, EvCaps
     }
     w->in_flight = true;
     w->fl.plan = plan;
+    w->fl.launched = true;
     w->fl.seq_next = w->seq_next;
     w->fl.dev_seq = w->dev_seq_pending;
     w->fl.cap = caps;

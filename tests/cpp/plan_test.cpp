@@ -1,7 +1,9 @@
 // Stand-alone test of csrc/gwaoi_plan.h: the flush's decisions as a pure function.  Part 1: named
 // flushes, the expected plan written out by hand from the conditions DESIGN.md ("The flush plan")
 // lists.  Part 2: the implications between the decisions, over every combination of the boolean
-// facts with the counts drawn from {0, 1, 300}.  Prints "ok".
+// facts with the counts drawn from {0, 1, 300}.  Part 3: chains of flushes, each planned with what the
+// one before it left behind (no overlap directly behind a flush whose special pass was not fused).
+// Prints "ok".
 #include "gwaoi_plan.h"
 
 #include <cstdio>
@@ -31,6 +33,7 @@ static FlushFacts steady() {
     f.tiles_prev = 8;
     f.all_plain_moves = true;  // (no run is anything else)
     f.gen_same = true;
+    f.prev_sp_fused = true;
     f.total_cells = 900;
     f.prev_grid_same = true;
     f.frame_grid_same = true;
@@ -159,6 +162,12 @@ static void scenarios() {
         f.mid_last = true;
         f.ovl_ok = false;
         CHECK(!plan_flush(f).ovl);
+        f.ovl_ok = true;
+        f.prev_sp_fused = false;  // the previous flush's special pass still has the flags to read
+        const FlushPlan q = plan_flush(f);
+        CHECK(!q.ovl && q.incr && q.sp_fused && q.ga_fused);
+        f.prev_sp_fused = true;
+        CHECK(plan_flush(f).ovl);
     }
     {  // 11. the special pass timed too
         FlushFacts f = speculative();
@@ -219,6 +228,7 @@ static void check_invariants(const FlushFacts &f) {
     ok &= !p.sp_fused || (p.incr && f.n_prev > 0);
     ok &= !p.ga_fused || p.incr;
     ok &= !p.ovl || (p.incr && f.ovl_ok && f.mid_last);
+    ok &= !p.ovl || f.prev_sp_fused;
     ok &= p.n_unique == (p.uniq ? f.n_ops : 0u);
     ok &= p.n_total == f.n_prev + p.n_app && p.n_new == f.n_alive;
     if (!ok && g_fail++ < 10)
@@ -231,7 +241,7 @@ static void invariants() {
     const uint32_t masks[5] = {0, 1u << ST_COMBINED, 1u << ST_SPECIAL, 1u << ST_GATHER, (1u << ST_N) - 1u};
     FlushFacts f{};
     f.total_cells = 900;
-    for (uint32_t bits = 0; bits < (1u << 12); ++bits) {
+    for (uint32_t bits = 0; bits < (1u << 13); ++bits) {
         f.all_plain_moves = bits & 1u;
         f.dev_struct = bits >> 1 & 1u;
         f.unique_moves = bits >> 2 & 1u;
@@ -244,6 +254,7 @@ static void invariants() {
         f.gen_same = bits >> 9 & 1u;
         f.prev_grid_same = bits >> 10 & 1u;
         f.frame_grid_same = bits >> 11 & 1u;
+        f.prev_sp_fused = bits >> 12 & 1u;
         for (uint32_t c = 0; c < 6561; ++c) {  // 3^8: the eight counts
             uint32_t d = c;
             auto next = [&] {
@@ -271,8 +282,61 @@ static void invariants() {
     }
 }
 
+// Part 3: chains.  Flush t+1 is planned with what flush t left behind, as tick_launch does it:
+// prev_sp_fused is flush t's sp_fused and mid_last says that flush t was launched speculatively.
+// The first flush of a chain is tick_begin's (not speculative), every later one is speculative.
+enum Step { STEADY, GRID_CHANGE, SPECIAL_TIMED, FORCE_RADIX };
+
+static void chain(const char *name, const Step *steps, int n) {
+    bool prev_fused = true, prev_spec = false;  // no flush preceded
+    int lost = 0;  // overlaps lost directly behind a non-fused flush
+    for (int t = 0; t < n; ++t) {
+        FlushFacts f = one_batch();
+        f.ovl_ok = t > 0;
+        f.mid_last = prev_spec;
+        f.prev_sp_fused = prev_fused;
+        if (steps[t] == GRID_CHANGE) f.prev_grid_same = f.frame_grid_same = false;
+        if (steps[t] == SPECIAL_TIMED) f.timing_mask = 1u << ST_SPECIAL;
+        if (steps[t] == FORCE_RADIX) f.force_radix = true;
+        const FlushPlan p = plan_flush(f);
+        bool ok = p.sp_fused == (steps[t] == STEADY);
+        // behind a speculative flush: overlapped exactly when both that flush and this one are fused
+        // (this one: incremental and untimed)
+        const bool want = prev_spec && prev_fused && steps[t] == STEADY;
+        ok &= p.ovl == want;
+        if (prev_spec && !prev_fused) {
+            ok &= !p.ovl;
+            ++lost;
+        }
+        if (!ok && g_fail++ < 10) std::printf("chain %s: flush %d: ovl %d sp_fused %d\n", name, t, p.ovl, p.sp_fused);
+        prev_fused = p.sp_fused;
+        prev_spec = f.ovl_ok;
+    }
+    // every chain below has a non-fused speculative flush with two flushes behind it: the first loses
+    // its overlap, the second (checked above: want) overlaps again
+    CHECK(lost >= 1);
+}
+
+static void chains() {
+    const Step grid[] = {STEADY, STEADY, GRID_CHANGE, STEADY, STEADY};
+    const Step timed[] = {STEADY, STEADY, SPECIAL_TIMED, STEADY, STEADY};
+    const Step radix[] = {STEADY, STEADY, FORCE_RADIX, STEADY, STEADY};
+    const Step twice[] = {STEADY, STEADY, GRID_CHANGE, GRID_CHANGE, STEADY, STEADY, SPECIAL_TIMED, STEADY, STEADY};
+    chain("grid change", grid, 5);
+    chain("special timed", timed, 5);
+    chain("force_radix", radix, 5);
+    chain("two grid changes, then timed", twice, 9);
+    // the overlap comes back: flush 4 of the first chain, planned on its own
+    FlushFacts f = speculative();
+    f.prev_sp_fused = false;
+    CHECK(!plan_flush(f).ovl && plan_flush(f).sp_fused);
+    f.prev_sp_fused = plan_flush(f).sp_fused;
+    CHECK(plan_flush(f).ovl);
+}
+
 int main() {
     scenarios();
+    chains();
     invariants();
     if (g_fail) return 1;
     std::printf("ok\n");

@@ -1344,6 +1344,49 @@ def test_cell_size_switch_keeps_parity_gpu(oracle_mod):
         assert B.debug_counters()["cell_size_switches"] == 0
 
 
+def test_incremental_sort_on_regrown_grid_gpu(oracle_mod):
+    """A grid with more scan tiles than the last incremental sort's, in arrays that are large enough
+    already: a scout far from a 4,096-entity crowd (12,000 cells, 12 scan tiles of 1,024 cells), home
+    again (the grid shrinks to the crowd: 6,200 cells, 7 tiles), out again.  The incremental sort's
+    scratch is laid out by the tile count, [entries per tile | changed cells per tile], and a sort
+    leaves the second half as it was: on the larger grid keygen's entries per tile must not meet the
+    smaller grid's leftovers (they did, and the flush ended in a live-count mismatch).  Events equal
+    the closed form at every flush; every flush but the three on a new grid is incremental."""
+    n = 4096
+    rng = np.random.default_rng(21)
+    x = rng.uniform(-1100, 1100, n).astype(np.float32)
+    z = rng.uniform(-1100, 1100, n).astype(np.float32)
+    x[0] = z[0] = np.float32(900.0)
+    slots = np.arange(n, dtype=np.uint32)
+    sp = np.zeros(n, np.uint32)
+    with World(n, cells_per_dist=3.0) as w:
+        s = w.space_create(D)
+        w.enter_batch(s, slots, x, z)
+        seq = 1 + np.arange(n, dtype=np.uint64)
+        nxt = n + 1
+        ge, _ = flush(w)
+        prev = oracle_mod.closed_form_pairs(x, z, seq, sp, {0: D})
+        np.testing.assert_array_equal(ge, prev)
+        cells = []
+        for t in range(11):
+            x = (x + rng.uniform(-1, 1, n).astype(np.float32)).astype(np.float32)
+            z = (z + rng.uniform(-1, 1, n).astype(np.float32)).astype(np.float32)
+            # out; home at flush 3 (the grid follows at flush 4: the box still holds the last flush's); out at 7
+            x[0] = np.float32(900.0 if 3 <= t < 7 else 11000.0)
+            order = rng.permutation(n).astype(np.uint32)
+            w.moved_batch(order, x[order], z[order])
+            seq[order] = nxt + np.arange(n, dtype=np.uint64)
+            nxt += n
+            ge, gl = flush(w)
+            cur = oracle_mod.closed_form_pairs(x, z, seq, sp, {0: D})
+            np.testing.assert_array_equal(ge, np.setdiff1d(cur, prev), err_msg=f"flush {t}: enters")
+            np.testing.assert_array_equal(gl, np.setdiff1d(prev, cur), err_msg=f"flush {t}: leaves")
+            prev = cur
+            cells.append(w.info()["total_cells"])
+        assert cells[0] == cells[3] > 8192 and 4096 < cells[4] == cells[6] <= 8192 and cells[7] == cells[10] > 8192, cells
+        assert w.debug_counters()["incremental_sorts"] == 8, cells
+
+
 def test_buffer_growths_then_second_world_gpu(oracle_mod):
     """Every host-side growth path once, in one sequence checked against the closed form at
     every flush, on a 4,096-slot world created with event_capacity=1024:
